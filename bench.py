@@ -19,16 +19,25 @@ forward; the one collective is a single all-gather of per-image metric records
 after the last step).  ``--config 1|3|4`` selects the other BASELINE configurations
 (WORKLOADS below) -- same code, same JSON.  Seeded random weights, fp32 results.
 
-Behind the timed region (N = 1; ``--no-extras`` skips them): the same steps strictly
-one after the other (``value_sequential``), >= 5 s of pipelined steps
-(``sustained_images_per_s``), one eager pass for the per-kernel table, and the
-workload again with every contraction on exact-fp32 arithmetic
-(``exact_fp32_images_per_s``, same process).
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+(``--dump-outputs DIR``) and prints the result line; nothing else.  With
+``--full``, behind the timed region: the same steps strictly one after the other
+(``value_sequential``), and (N = 1; ``--no-extras`` skips them) >= 5 s of
+pipelined steps (``sustained_images_per_s``), one eager pass for the per-kernel
+table, the workload again with every contraction on exact-fp32 arithmetic
+(``exact_fp32_images_per_s``, same process), the other BASELINE configurations
+and small batches, and the CPU oracle (``--no-cpu-baseline`` skips it).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
-objects: "roofline" (dominant hand-written kernel, live HIP-event timing inside
-the timed region) and "cpu_baseline" (the CPU oracle timed on the host cores on
-a bounded sample, N = 1 only).
+Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+"roofline" (dominant hand-written kernel, live HIP-event timing inside the timed
+region) and, with ``--full``, "cpu_baseline" (the CPU oracle timed on the host
+cores on a bounded sample, N = 1 only).
+
+``--dump-outputs DIR``: what the timed path returned in its last step -- depth,
+bin edges and the per-image metric records -- as DIR/<name>.npy (float32), at most
+64 MB in all (a larger array is stored as a fixed, seeded sample of its
+elements).  The inputs are seeded, so two builds run with the same arguments can
+be compared output for output.
 """
 from __future__ import annotations
 
@@ -446,6 +455,32 @@ def exact_fp32_pass(device, wl, img, gt, box, B, default_depth, steps=10):
     return steps * B / dt, depth, rel
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays, seed=1234):
+    """Write each array of ``arrays`` (name -> tensor) as ``dirname/<name>.npy``: float32, float64 kept as float64.  The
+    smallest arrays are written whole; an array larger than its share of DUMP_BUDGET_BYTES is written as a sample of its
+    flattened elements at fixed, seeded positions (the same positions for the same shape on every run).  -> {name: note}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cpu = {k: v.detach().cpu().numpy() for k, v in arrays.items() if v is not None}
+    cpu = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in cpu.items()}
+    left, notes = DUMP_BUDGET_BYTES, {}
+    for i, (name, x) in enumerate(sorted(cpu.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(cpu) - i) - 256               # (room for the .npy header)
+        if x.nbytes > share:
+            k = share // x.itemsize
+            idx = np.sort(np.random.default_rng(seed).choice(x.size, size=k, replace=False))
+            notes[name] = f"{k} of {x.size} elements of {list(x.shape)} (seeded sample, seed {seed})"
+            x = x.reshape(-1)[idx]
+        else:
+            notes[name] = f"{list(x.shape)} whole"
+        np.save(os.path.join(dirname, name + ".npy"), x)
+        left -= x.nbytes + 256
+    return notes
+
+
 def cpu_share() -> int:
     """CPUs this job may really use: the affinity mask, capped by the cgroup CPU quota (v2 cpu.max / v1 cfs quota) when there is one."""
     n = len(os.sched_getaffinity(0))
@@ -567,11 +602,18 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(WORKLOADS),
                     help="BASELINE.json configs[i] as the workload; 2 (default) is the configuration the metric is quoted on")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default: the config's per-GPU batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also measure everything that is not the headline figure: the sequential rate, "
+                         "the sustained rate, the per-kernel eager pass, the exact-fp32 route, the other configurations and "
+                         "batches, the CPU baseline (default: set up, warm up, time the steps, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds of CPU time the cpu_baseline leg may spend on its batched passes")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the legs behind the timed region (sustained run, exact-fp32 route, per-kernel eager pass)")
-    ap.add_argument("--sustain-seconds", type=float, default=5.0, help="length of the sustained-rate leg after the timed region")
+                    help="--full without the legs behind the timed region (sustained run, exact-fp32 route, per-kernel eager pass, "
+                         "other configurations)")
+    ap.add_argument("--sustain-seconds", type=float, default=5.0, help="length of the sustained-rate leg after the timed region (--full)")
     ap.add_argument("--eager", action="store_true",
                     help="dispatch every launch eagerly instead of replaying the forward as a hipGraph (default: graph "
                          "segments + the roofline convolution and the bin head as eager, event-timed launches)")
@@ -581,9 +623,11 @@ def main():
                          "of one batch (token path, squeeze-excite, late 1x1 layers) run under the compute-bound ones of "
                          "another.  1 = strictly one step after the other")
     ap.add_argument("--leg-seconds", type=float, default=1.0,
-                    help="length of each leg of configs_all / small_batch behind the timed region (N = 1, skipped by --no-extras)")
+                    help="length of each leg of configs_all / small_batch behind the timed region (--full, N = 1, skipped by --no-extras)")
     ap.add_argument("--stub-cpu", action="store_true", help=argparse.SUPPRESS)   # plumbing test only (gloo, no model)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))     # before any GPU call (and before torch is imported) here
@@ -618,6 +662,7 @@ def main():
     launch_mode = "eager"
     island = f"conv3x3|{B},{wl.h},{wl.w},128,128"
     gt = box = None
+    last_out = [None]                                  # the model output of the latest step (GPU path)
     if a.stub_cpu:
         # the slot bookkeeping of the pipelined mode (slots take the steps round-robin after the first ROOFLINE_STEPS) without a GPU
         work = [StubWorkload(B) for _ in range(max(1, a.inflight))]
@@ -676,6 +721,7 @@ def main():
             with torch.cuda.stream(streams[slot]):
                 out = slots[slot](img)
                 step_flags.append(getattr(slots[slot], "last_flag", None))
+                last_out[0] = out                          # (--dump-outputs: the bin edges travel with the depth)
                 return out.depth_pred, hip_ops.depth_metrics(out.depth_pred, gt, wl.min_depth, wl.max_depth, crop=box,
                                                              first_image_id=first_id)
 
@@ -729,6 +775,15 @@ def main():
     table = dp.gather_records(torch.cat(records, 0), world, n_total=world * a.steps * B)      # the one collective of the job
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs:
+        # the last timed step's outputs, before anything behind the timed region replays the slots (this rank's shard)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        outs = {"depth_pred" + sfx: depth, "metric_records" + sfx: records[-1]}
+        if last_out[0] is not None:
+            outs["bin_edges" + sfx] = last_out[0].bin_edges
+        dumped = dump_outputs(a.dump_outputs, outs)
+        log(f"outputs of the last timed step written to {a.dump_outputs}: {dumped}")
     timing = {}
     step_latency_ms = sequential_ips = sustained_ips = sustained_s = None
     exact = None
@@ -748,75 +803,78 @@ def main():
             timed_steps = a.steps if nslot == 1 else ROOFLINE_STEPS
             live = {k: (v[0] / timed_steps * a.steps, v[1]) for k, v in timing.items()}
             hip_ops.enable_timing(False)
-            # one batch at a time: what a caller with a single forward in flight gets -- a capture of its own, made the way
-            # such a caller makes it (in_flight = 1: the lone-batch side streams on where the hardware-queue count allows), on slot 0's stream
-            seq_step = lambda: step(0, 0)
-            if nslot > 1:
-                from objcavit_amd.graph import GraphedGraphBins
-                lone = GraphedGraphBins(model, img, in_flight=1)
+            if not a.full:
+                timing = {}
+            else:
+                # one batch at a time: what a caller with a single forward in flight gets -- a capture of its own, made the way
+                # such a caller makes it (in_flight = 1: the lone-batch side streams on where the hardware-queue count allows), on slot 0's stream
+                seq_step = lambda: step(0, 0)
+                if nslot > 1:
+                    from objcavit_amd.graph import GraphedGraphBins
+                    lone = GraphedGraphBins(model, img, in_flight=1)
 
-                def seq_step():
-                    with torch.cuda.stream(lone.stream):
-                        out = lone(img)
-                        return out.depth_pred, hip_ops.depth_metrics(out.depth_pred, gt, wl.min_depth, wl.max_depth, crop=box, first_image_id=0)
-                for _ in range(2):
+                    def seq_step():
+                        with torch.cuda.stream(lone.stream):
+                            out = lone(img)
+                            return out.depth_pred, hip_ops.depth_metrics(out.depth_pred, gt, wl.min_depth, wl.max_depth, crop=box, first_image_id=0)
+                    for _ in range(2):
+                        seq_step()
+                    torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                seq_step()
+                torch.cuda.synchronize()
+                step_latency_ms = (time.perf_counter() - t1) * 1e3          # one batch alone, submit -> metrics record
+                nseq = max(4, a.steps)                                       # reference: the same steps strictly one after the other
+                t1 = time.perf_counter()
+                for _ in range(nseq):
                     seq_step()
                 torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            seq_step()
-            torch.cuda.synchronize()
-            step_latency_ms = (time.perf_counter() - t1) * 1e3          # one batch alone, submit -> metrics record
-            nseq = max(4, a.steps)                                       # reference: the same steps strictly one after the other
-            t1 = time.perf_counter()
-            for _ in range(nseq):
-                seq_step()
-            torch.cuda.synchronize()
-            sequential_ips = nseq * B / (time.perf_counter() - t1)
-            if nslot > 1:
-                del lone
-            if not a.no_extras:
-                # sustained rate: the timed region above is a fraction of a second on a cold part; here the same pipelined
-                # steps run for >= sustain_seconds (the chip settles at its power-capped clock: profiles/r02_power_probe.txt)
-                per_round = max(nslot, int(0.25 / max(dt / a.steps, 1e-4)) // nslot * nslot)
-                t1 = time.perf_counter()
-                n_sus = 0
-                while time.perf_counter() - t1 < a.sustain_seconds:
-                    for k in range(per_round):
-                        step(0, k % nslot)
-                    torch.cuda.synchronize()
-                    n_sus += per_round
-                sustained_s = time.perf_counter() - t1
-                sustained_ips = n_sus * B / sustained_s
-                log(f"sustained leg: {n_sus} steps in {sustained_s:.2f} s = {sustained_ips:.1f} img/s")
-                # per-kernel table: one stream (a launch bracketed while a side stream shares the chip would time the sharing)
-                saved = {"OCV_FORKS": os.environ.get("OCV_FORKS")}
-                os.environ["OCV_FORKS"] = "0"
-                try:
-                    for _ in range(2):
-                        model(img)                       # (scratch of the one-stream order: allocated outside the timed pass)
-                    torch.cuda.synchronize()
-                    hip_ops.enable_timing(True)
-                    for _ in range(3):
-                        model(img)
-                finally:
-                    for k, v in saved.items():
-                        if v is None:
-                            os.environ.pop(k, None)
-                        else:
-                            os.environ[k] = v
-                extra = hip_ops.timing_results()
-                timing = {k: (v[0] / 3 * a.steps, v[1]) for k, v in extra.items()}
-            else:
-                timing = {}
+                sequential_ips = nseq * B / (time.perf_counter() - t1)
+                if nslot > 1:
+                    del lone
+                if not a.no_extras:
+                    # sustained rate: the timed region above is a fraction of a second on a cold part; here the same pipelined
+                    # steps run for >= sustain_seconds (the chip settles at its power-capped clock: profiles/r02_power_probe.txt)
+                    per_round = max(nslot, int(0.25 / max(dt / a.steps, 1e-4)) // nslot * nslot)
+                    t1 = time.perf_counter()
+                    n_sus = 0
+                    while time.perf_counter() - t1 < a.sustain_seconds:
+                        for k in range(per_round):
+                            step(0, k % nslot)
+                        torch.cuda.synchronize()
+                        n_sus += per_round
+                    sustained_s = time.perf_counter() - t1
+                    sustained_ips = n_sus * B / sustained_s
+                    log(f"sustained leg: {n_sus} steps in {sustained_s:.2f} s = {sustained_ips:.1f} img/s")
+                    # per-kernel table: one stream (a launch bracketed while a side stream shares the chip would time the sharing)
+                    saved = {"OCV_FORKS": os.environ.get("OCV_FORKS")}
+                    os.environ["OCV_FORKS"] = "0"
+                    try:
+                        for _ in range(2):
+                            model(img)                       # (scratch of the one-stream order: allocated outside the timed pass)
+                        torch.cuda.synchronize()
+                        hip_ops.enable_timing(True)
+                        for _ in range(3):
+                            model(img)
+                    finally:
+                        for k, v in saved.items():
+                            if v is None:
+                                os.environ.pop(k, None)
+                            else:
+                                os.environ[k] = v
+                    extra = hip_ops.timing_results()
+                    timing = {k: (v[0] / 3 * a.steps, v[1]) for k, v in extra.items()}
+                else:
+                    timing = {}
             timing.update(live)
         hip_ops.enable_timing(False)
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             log("exact-fp32 route ...")
             ips, exact_depth, rel = exact_fp32_pass(device, wl, img, gt, box, B, default_depth)
             exact = dict(images_per_s=round(ips, 1), depth=exact_depth, max_rel_vs_default_route=rel)
             log(f"exact-fp32 route: {ips:.1f} img/s, max rel vs default route {rel:.2e}")
         legs = None
-        if world == 1 and not a.no_extras and not a.eager and a.config == 2 and a.batch is None:
+        if a.full and world == 1 and not a.no_extras and not a.eager and a.config == 2 and a.batch is None:
             # Every other BASELINE configuration and the reference's own batch sizes, on the driver's clock:
             # configs[1] / [3] / [4] with this run's --inflight, configs[2] at bs 1 and bs 2 (= image + mirror) one step at a time
             # and at bs 16 one step at a time.  ~leg-seconds each + a capture; slots of the timed region are released first.
@@ -885,7 +943,7 @@ def main():
         res = {
             "metric": f"images/sec ({W}x{H}, bs={B}) forward depth inference, {inflight_note}; AbsRel vs CPU ref",
             "value": value, "unit": "images/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "full": a.full,
             "scaling": "weak", "vs_baseline": None,
             "dtype": "stub" if a.stub_cpu else "f32 (fp16 / bf16 split contractions)",
             "data": "stub" if a.stub_cpu else "synthetic",
@@ -918,6 +976,8 @@ def main():
                        "value_sequential": (None if sequential_ips is None else round(sequential_ips * world, 1)) if nslot > 1 else value},
             "metrics_gathered": dp.summarise(table),
         }
+        if dumped is not None:
+            res["outputs_dumped"] = {"dir": a.dump_outputs, "arrays": dumped}
         if not a.stub_cpu:
             res["dtype_note"] = ("fp32 results; the decoder's / heads' 3x3, tap-GEMM and 16x16-patch convolutions run as two-term FP16 splits "
                                  "(round 4: hi*hi + hi*lo + lo*hi on v_mfma_*_f16, fp32 accumulate, product error <= 2^-22; weights scaled per "
@@ -946,7 +1006,7 @@ def main():
             if exact is not None:
                 res["exact_fp32_images_per_s"] = exact["images_per_s"]
                 res["exact_fp32_max_rel_vs_default_route"] = exact["max_rel_vs_default_route"]
-            if world == 1 and not a.no_cpu_baseline:
+            if a.full and world == 1 and not a.no_cpu_baseline:
                 feats, boxes, _ = model.object_provider(img)
                 log("cpu baseline ...")
                 cb, absrel, maxrel = cpu_baseline(sd, img_cpu, feats, boxes, depth, wl, budget_s=a.cpu_budget)

@@ -3,7 +3,7 @@
 bench.py JSON line minus the bulky dtype note) and profiles/<tag>_cfg<c>_step_breakdown.txt (rocprofv3 kernel trace, fastest
 step, one row per launch grid).
 
-    python tools/make_configs_profile.py r03
+    python tools/make_configs_profile.py r03 [OUT]        (OUT: tools/profile_configs.sh's output root, default runs/)
 """
 import json
 import os
@@ -15,17 +15,17 @@ sys.path.insert(0, os.path.join(ROOT, "profiles"))
 import summarize  # noqa: E402
 
 
-def main(tag):
+def main(tag, root):
     out = {}
     for c in (1, 2, 3, 4):
-        p = os.path.join(ROOT, "gpurun_out", "configs", f"cfg{c}.json")
+        p = os.path.join(root, "configs", f"cfg{c}.json")
         if not os.path.exists(p):
             continue
         line = [ln for ln in open(p).read().splitlines() if ln.startswith("{")][-1]
         d = json.loads(line)
         d.pop("dtype_note", None)
         out[f"configs[{c}]"] = d
-        src = os.path.join(ROOT, "gpurun_out", f"prof_cfg{c}")
+        src = os.path.join(root, f"prof_cfg{c}")
         if os.path.isdir(os.path.join(src, "kt")):
             summarize.main(src, f"{tag}_cfg{c}")
             ks = os.path.join(ROOT, "profiles", f"{tag}_cfg{c}_kernel_stats.csv")
@@ -40,4 +40,4 @@ def main(tag):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "r03")
+    main(sys.argv[1] if len(sys.argv) > 1 else "r03", sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "runs"))
