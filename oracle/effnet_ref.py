@@ -1,7 +1,8 @@
 """Functional restatement of the ``tf_efficientnet_b5_ap`` encoder as wrapped by
 the reference's ``Encoder`` (ORACLE -- test infrastructure only).
 
-PARITY UNPINNED for the encoder arithmetic.  The reference fetches the
+PINNED by tests/golden G8 against an independent implementation, at H and W
+multiples of 32; odd sizes stay restated only.  The reference fetches the
 architecture source and the weights at run time with
 ``torch.hub.load('rwightman/gen-efficientnet-pytorch', 'tf_efficientnet_b5_ap',
 pretrained=True)`` (modules/DenseFeatureExtractor.py:149; hub default branch,
@@ -23,9 +24,17 @@ family (EfficientNet, Tan & Le 2019; geffnet "tf_" variants):
   squeeze-excite in every block, reduction = 0.25 x block INPUT channels,
   swish inside, sigmoid gate; residual when stride 1 and in == out.
 
-What IS pinned: the order in which ``Encoder.forward`` collects activations
+The pins: the order in which ``Encoder.forward`` collects activations
 (modules/DenseFeatureExtractor.py:18-27) -- tests/golden G4 runs the
-reference's own ``Encoder`` + ``Decoder`` classes around a local backbone.
+reference's own ``Encoder`` + ``Decoder`` classes around a local backbone --
+and the arithmetic: G8 runs ``transformers``' ``EfficientNetModel`` (same
+layout from its config; a separate statement of the same published model) in
+float64 on the same seeded weights at 480 x 640 and 352 x 1216, with the
+reference's own ``Decoder`` on its activations; this restatement meets it to
+<= 1.4e-6 relative to max |x| at the stem, every stage end, conv_head and the
+decoder output (tests/test_oracle_golden.py::test_g8_effnet_b5_oracle).  That
+implementation pads stride-2 convolutions statically, which equals TF "SAME"
+only when every stride-2 input is even: H and W multiples of 32.
 Key names follow geffnet's module names so a real checkpoint's keys line up.
 """
 from __future__ import annotations

@@ -10,6 +10,13 @@ runs on CPU in eval() + no_grad, and the OUTPUTS are stored.  The oracle
 restatement (oracle/restate.py) is run on the same values and must agree; the
 max deviation per case is printed and stored in the fixture.  The fixtures
 hold data only: seeds, shapes, key/shape listings and output arrays.
+
+G8 is the exception to "the reference's own modules": the reference fetches its
+EfficientNet-B5 encoder at run time, so G8 runs an INDEPENDENT implementation of
+that encoder (``transformers``' ``EfficientNetModel``, built from its config, no
+download) in float64 on the product's seeded weights, and the reference's own
+``Decoder`` in float64 on its activations.  It pins ``oracle/effnet_ref.py`` and
+``objcavit_amd/modules/efficientnet.py`` at H and W multiples of 32.
 """
 from __future__ import annotations
 
@@ -339,7 +346,156 @@ def g7_relsize():
                              clauses=[[c for c in ci] for ci in clauses]), **arrays)
 
 
+# ------------------------------------------------------------------ G8 EfficientNet-B5 encoder, independent implementation
+G8_CASES = {
+    # tag: (input shape, seed)
+    "nyu_b1": ((1, 3, 480, 640), 81),        # main.py's batch: the small-batch routes
+    "kitti_b4": ((4, 3, 352, 1216), 82),     # KITTI: late stages 22 x 76 and 11 x 38, pre-split project route
+    "nyu_b16": ((16, 3, 480, 640), 83),      # configs[2], the benchmark's operating point
+}
+G8_TENSORS = ("f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "out")
+G8_HF_STAGE_ENDS = (3, 8, 13, 20, 27, 36, 39)   # hidden_states index of the end of stages 0 .. 6
+G8_SAMPLES = 8192
+
+
+def _g8_sample_index(shape, seed, tag):
+    """int16 [N, 4] (n, c, h, w): the 4 corners + 4 edge midpoints of 64 seeded (image, channel) pairs, the whole one-pixel
+    frame of 2 seeded pairs, the rest uniform with image n = i mod B (every image represented)."""
+    B, C, H, W = shape
+    rs = gen._rs(seed, "g8:" + tag)
+    n, c = rs.randint(0, B, 64), rs.randint(0, C, 64)
+    hh = np.array([0, 0, H - 1, H - 1, 0, H - 1, H // 2, H // 2])
+    ww = np.array([0, W - 1, 0, W - 1, W // 2, W // 2, 0, W - 1])
+    parts = [np.stack([np.repeat(n, 8), np.repeat(c, 8), np.tile(hh, 64), np.tile(ww, 64)], 1)]
+    fh = np.concatenate([np.zeros(W, int), np.full(W, H - 1), np.arange(1, H - 1), np.arange(1, H - 1)])
+    fw = np.concatenate([np.arange(W), np.arange(W), np.zeros(H - 2, int), np.full(H - 2, W - 1)])
+    for n1, c1 in zip(rs.randint(0, B, 2), rs.randint(0, C, 2)):
+        parts.append(np.stack([np.full(fh.size, n1), np.full(fh.size, c1), fh, fw], 1))
+    r = G8_SAMPLES - sum(len(q) for q in parts)
+    parts.append(np.stack([np.arange(r) % B, rs.randint(0, C, r), rs.randint(0, H, r), rs.randint(0, W, r)], 1))
+    idx = np.concatenate(parts)
+    assert len(idx) == G8_SAMPLES and idx.max() < 2 ** 15
+    return idx.astype(np.int16)
+
+
+def _g8_hf_model():
+    """transformers' EfficientNetModel with the B5 layout, from its config alone (offline, no weights fetched)."""
+    os.environ["HF_HUB_OFFLINE"] = "1"
+    os.environ["TRANSFORMERS_OFFLINE"] = "1"
+    # ref_import's torchvision stub (no __spec__) would break transformers' optional-package probe: hidden while importing
+    stubs = {k: sys.modules.pop(k) for k in list(sys.modules) if k.split(".")[0] == "torchvision"}
+    try:
+        import transformers
+        from transformers import EfficientNetConfig, EfficientNetModel
+    finally:
+        sys.modules.update(stubs)
+    cfg = EfficientNetConfig(width_coefficient=1.6, depth_coefficient=2.2, hidden_dim=2048)
+    return EfficientNetModel(cfg).eval(), cfg, transformers.__version__
+
+
+def _g8_load_hf(hf, product):
+    """The product's seeded encoder weights into the HF model, paired in order shape for shape; returns the product key names
+    in pairing order."""
+    enc = {k: v for k, v in product.state_dict().items() if k.startswith("encoder.original_model.")
+           and not k.endswith("num_batches_tracked")}
+    own = hf.state_dict()
+    hf_keys = [k for k in own if not k.endswith("num_batches_tracked") and not k.startswith("encoder.top_bn.")]
+    assert len(enc) == len(hf_keys) == 732, (len(enc), len(hf_keys))
+    pairs = list(zip(enc, hf_keys))
+    for pk, hk in pairs:
+        assert tuple(enc[pk].shape) == tuple(own[hk].shape), (pk, hk)
+    pd = dict(pairs)
+    assert pd["encoder.original_model.conv_stem.weight"] == "embeddings.convolution.weight"
+    assert pd["encoder.original_model.conv_head.weight"] == "encoder.top_conv.weight"
+    sd = {hk: enc[pk] for pk, hk in pairs}
+    sd.update({k: v for k, v in own.items() if k.endswith("num_batches_tracked") and not k.startswith("encoder.top_bn.")})
+    res = hf.load_state_dict(sd, strict=False)
+    assert not res.unexpected_keys, res.unexpected_keys
+    assert sorted(res.missing_keys) == sorted(f"encoder.top_bn.{p}" for p in ("weight", "bias", "running_mean", "running_var")), res
+    hf.double()
+    return [pk for pk, _ in pairs]
+
+
+def g8_effnet_b5():
+    import hashlib
+    import time
+    from objcavit_amd.modules.DenseFeatureExtractor import DenseFeatureExtractor
+    from oracle import effnet_ref
+    dfe = ref_import.load("DenseFeatureExtractor")
+    for tag, (shape, seed) in G8_CASES.items():
+        t0 = time.time()
+        B = shape[0]
+        m = DenseFeatureExtractor(make_args()).eval()
+        sd = gen.load_into(m, seed)
+        hf, cfg, hf_version = _g8_hf_model()
+        names = _g8_load_hf(hf, m)
+        dec = dfe.Decoder(num_classes=128, num_features=2048, bottleneck_features=2048, mode=None,
+                          encoder_name="efficientnet-b5", do_final_upscale=None).eval()
+        dec.load_state_dict({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}, strict=True)
+        dec.double()
+        img = gen.randn("img", shape, seed)
+        idx, shapes, arrays = None, None, {}
+        absmax = {t: 0.0 for t in G8_TENSORS}
+        err = {t: 0.0 for t in G8_TENSORS}       # max |fp32 oracle - fp64| over the whole tensor
+        err_dec = 0.0                            # max |restate.decoder_forward(oracle) - reference Decoder(HF)|
+        for i in range(B):
+            x = img[i:i + 1]
+            hs = hf(pixel_values=x.double(), output_hidden_states=True).hidden_states
+            assert len(hs) == 40
+            f = {"f3": hs[0]}
+            f.update({f"f{4 + s}": hs[j] for s, j in enumerate(G8_HF_STAGE_ENDS)})
+            f["f11"] = hf.encoder.top_conv(hs[39])
+            feats = [None] * 16
+            for j in (4, 5, 6, 8, 11):
+                feats[j] = f[f"f{j}"]
+            f["out"] = dec(feats)
+            ref = effnet_ref.encoder_features(x, sd, "encoder.original_model.")
+            out32 = restate.decoder_forward(ref, sd, "decoder.")
+            mine = {f"f{j}": ref[j] for j in range(3, 12)}
+            mine["out"] = out32
+            if idx is None:
+                shapes = {t: [B] + list(f[t].shape[1:]) for t in G8_TENSORS}
+                idx = {t: _g8_sample_index(shapes[t], seed, t) for t in G8_TENSORS}
+                for t in G8_TENSORS:
+                    arrays[t + "_val"] = np.zeros(len(idx[t]), np.float64)
+                    arrays[t + "_mean"] = np.zeros(shapes[t][:2], np.float64)
+                    arrays[t + "_rms"] = np.zeros(shapes[t][:2], np.float64)
+            for t in G8_TENSORS:
+                v = f[t][0]
+                assert list(v.shape) == shapes[t][1:] and list(mine[t].shape[1:]) == shapes[t][1:], t
+                sel = idx[t][:, 0] == i
+                ii = torch.from_numpy(idx[t][sel].astype(np.int64))
+                arrays[t + "_val"][sel] = _np(v[ii[:, 1], ii[:, 2], ii[:, 3]])
+                arrays[t + "_mean"][i] = _np(v.mean((1, 2)))
+                arrays[t + "_rms"][i] = _np(v.pow(2).mean((1, 2)).sqrt())
+                absmax[t] = max(absmax[t], float(v.abs().max()))
+                err[t] = max(err[t], float((mine[t][0].double() - v).abs().max()))
+            err_dec = max(err_dec, float((out32[0].double() - f["out"][0]).abs().max()))
+        dev = {t: err[t] / absmax[t] for t in G8_TENSORS}
+        dev_dec = err_dec / absmax["out"]
+        print(f"G8 EfficientNet-B5[{tag}] {list(shape)}: effnet_ref (fp32) vs HF (fp64), whole tensors, rel to max|x|: "
+              + " ".join(f"{t} {d:.2e}" for t, d in dev.items()))
+        print(f"G8 EfficientNet-B5[{tag}] restate.decoder_forward(effnet_ref) vs reference Decoder(HF), fp64: {dev_dec:.2e}"
+              f"  ({time.time() - t0:.0f} s)")
+        assert max(dev.values()) <= 1e-5 and dev_dec <= 1e-5
+        out = {}
+        for t in G8_TENSORS:
+            out[t + "_idx"] = idx[t]
+            out[t + "_val"] = arrays[t + "_val"].astype(np.float32)
+            out[t + "_mean"] = arrays[t + "_mean"].astype(np.float32)
+            out[t + "_rms"] = arrays[t + "_rms"].astype(np.float32)
+            out[t + "_absmax"] = np.array(absmax[t], np.float64)
+        listing = "\n".join(f"{k}:{list(sd[k].shape)}" for k in names)
+        _save(f"g8_effnet_b5_{tag}",
+              dict(seed=seed, input_shape=list(shape), shapes=shapes, tensors=list(G8_TENSORS), hf_version=hf_version,
+                   hf_config=cfg.to_diff_dict(), hf_stage_ends=list(G8_HF_STAGE_ENDS), n_keys=len(names),
+                   keys_sha256=hashlib.sha256(listing.encode()).hexdigest(), first_key=names[0], last_key=names[-1],
+                   dev_effnet_ref=dev, dev_decoder=dev_dec),
+              **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g5u", "g6", "g7"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g5u", "g6", "g7", "g8"]
     for w in which:
-        {"g1": g1_mvit, "g2": g2_saca, "g3": g3_objcavit, "g4": g4_decoder, "g5": g5_adabins, "g5u": g5_adabins_final_upscale, "g6": g6_validation, "g7": g7_relsize}[w]()
+        {"g1": g1_mvit, "g2": g2_saca, "g3": g3_objcavit, "g4": g4_decoder, "g5": g5_adabins, "g5u": g5_adabins_final_upscale, "g6": g6_validation, "g7": g7_relsize,
+         "g8": g8_effnet_b5}[w]()

@@ -37,3 +37,29 @@ def max_rel(a, b):
 
 def state_dict_from(meta_shapes, seed, gains=()):
     return gen.fill({k: tuple(v) for k, v in meta_shapes.items()}, seed, gains)
+
+
+def golden_sample_dev(x, z, t, images=None):
+    """(sampled deviation, moment deviation) of a [B, C, H, W] tensor ``x`` (NCHW or channels_last, CPU or GPU) against the
+    stored tensor ``t`` of a sampled fixture (G8: ``<t>_idx`` (n, c, h, w), ``<t>_val``, per (image, channel) ``<t>_mean`` /
+    ``<t>_rms``), both as max |difference| / ``<t>_absmax`` -- normalised like rel_dev on the whole tensor.  ``images``: the
+    fixture's image indices that x's batch entries hold, in order (x a subset of the batch); None: x is the whole batch."""
+    idx = torch.from_numpy(z[t + "_idx"].astype(np.int64))
+    mean, rms = torch.from_numpy(z[t + "_mean"]).double(), torch.from_numpy(z[t + "_rms"]).double()
+    val = torch.from_numpy(z[t + "_val"]).double()
+    if images is not None:
+        pos = torch.full((mean.shape[0],), -1, dtype=torch.int64)
+        pos[torch.as_tensor(list(images))] = torch.arange(len(images))
+        sel = pos[idx[:, 0]] >= 0
+        idx, val = idx[sel], val[sel]
+        idx[:, 0] = pos[idx[:, 0]]
+        mean, rms = mean[list(images)], rms[list(images)]
+    assert tuple(x.shape[:2]) == tuple(mean.shape), (tuple(x.shape), tuple(mean.shape))
+    n, c, h, w = idx.to(x.device).unbind(1)
+    got = x[n, c, h, w].double().cpu()
+    xd = x.detach().double()
+    got_mean, got_rms = xd.mean((2, 3)).cpu(), xd.pow(2).mean((2, 3)).sqrt().cpu()
+    den = float(z[t + "_absmax"])
+    samp = float((got - val).abs().max()) / den
+    mom = max(float((got_mean - mean).abs().max()), float((got_rms - rms).abs().max())) / den
+    return samp, mom
