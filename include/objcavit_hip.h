@@ -41,6 +41,7 @@ typedef void* ocv_stream_t;
 
 #define OCV_ABI_VERSION 5 /* 5: round 6 ADDED ocv_attention_set_dispatch (the library reads no environment variable any more),
  * ocv_conv3x3_packed_taps_k / ocv_conv3x3_split_packed_taps_fwd; nothing removed or changed: a caller built against 4 keeps working;
+ * later ADDED (still 5: a new symbol changes nothing for an existing caller) ocv_conv3x3_nhwc_strided_fwd (EfficientNetV2);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -467,6 +468,17 @@ int ocv_conv_nhwc_fwd(const float* x1, int C1, const float* x2, int C2, const vo
 int ocv_conv_nhwc_exact_fwd(const float* x1, int C1, const float* x2, int C2, const float* w_tap_major, const float* bias,
                             const float* residual, float* y, int B, int H, int W, int Cout, int ksize, int act,
                             ocv_stream_t stream);
+/* 3x3 convolution with stride 1 or 2 and explicit zero padding (pad_t rows on top, pad_l columns on the left; the output
+ * size Ho x Wo is the caller's: (Ho - 1) stride - pad_t < H, (Wo - 1) stride - pad_l < W, pads < 3) of an NHWC fp32 tensor
+ * on the split-bf16 matrix cores (three v_mfma_f32_32x32x16_bf16 per block, fp32 accumulation, as ocv_conv_nhwc_fwd):
+ * y = act(conv(x) + bias) (+ residual).  x [B,H,W,Cin], Cin a positive multiple of 4; w_hi / w_lo bf16 [9][Cout][Cp],
+ * Cp = Cin rounded up to 32 (ocv_conv_nhwc_fwd's weights); bias [Cout] nullable; residual (nullable) and y
+ * [B,Ho,Wo,Cout].  act: OCV_ACT_NONE / RELU / LEAKY_RELU / SILU.  Returns -1 (ocv_last_error) on a bad argument.
+ * Replaces the 3x3 convolution (+ folded BN + SiLU, + skip) of torchvision's FusedMBConv (EfficientNetV2 stages 1 - 3,
+ * symmetric padding 1), reference modules/DenseFeatureExtractor.py:159-166. */
+int ocv_conv3x3_nhwc_strided_fwd(const float* x, int Cin, const void* w_hi, const void* w_lo, const float* bias,
+                                 const float* residual, float* y, int B, int H, int W, int Cout, int stride, int pad_t,
+                                 int pad_l, int Ho, int Wo, int act, ocv_stream_t stream);
 
 /* Expand 1x1 convolution (+ bias = folded BN, SiLU) and the depthwise k x k convolution (+ bias, SiLU) behind it, fused:
  * the expanded tensor is never written to memory.  x [B,H,W,Cin] NHWC fp32, Cin a multiple of 8 in [24, 64];

@@ -37,6 +37,8 @@
 //              selects), split it into hi/lo, fetch the pre-split weight chunk, write the other LDS buffer.
 // One consumer and one producer wave share each SIMD: matrix pipe and VALU run side by side; one barrier per step.
 // Workgroup ids are remapped so that the N-tiles of one pixel tile run on the same XCD and share its L2.
+// conv_strided.hip holds a copy of conv_igemm_kernel's schedule (tile map, consumer loop, two producer groups) with a strided
+// gather (stride 1 / 2, explicit padding: EfficientNetV2's Fused-MBConv): a fix to the schedule here belongs there too.
 #include <stdlib.h>
 
 #include "common.hpp"

@@ -503,4 +503,37 @@ def conv_nhwc(x1: torch.Tensor, x2: Optional[torch.Tensor], w_hi: torch.Tensor, 
     return y
 
 
+def conv3x3_strided(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor, bias: Optional[torch.Tensor], stride: int,
+                    padding: Tuple[int, int], act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
+                    out_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """act(conv3x3(x, stride, zero padding (pad_t, pad_l) on top / left) + bias) (+ residual) on the split-bf16 matrix cores
+    (ocv_conv3x3_nhwc_strided_fwd).  Output size ``out_hw`` = (Ho, Wo); None: (H + 2 pad_t - 3) // stride + 1 (symmetric
+    padding, torchvision's (k - 1) // 2).  A larger output (TF "SAME": ceil(H / stride)) pads the bottom / right with zeros.
+    x [B, Cin, H, W] channels_last fp32, Cin % 4 == 0; (w_hi, w_lo) = prep_conv_weight(w) [9, Cout, Cp]."""
+    lib = _lib.load()
+    x = _nhwc(x, "x")
+    B, Cin, H, W = x.shape
+    for n, t in (("w_hi", w_hi), ("w_lo", w_lo)):
+        _req(t, n, torch.bfloat16)
+    taps, Cout, Cp = w_hi.shape
+    if w_lo.shape != w_hi.shape or taps != 9 or Cp != (Cin + 31) // 32 * 32:
+        raise ValueError(f"conv3x3_strided: weights {tuple(w_hi.shape)} do not match {Cin} input channels")
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.numel() != Cout:
+            raise ValueError("conv3x3_strided: bias size mismatch")
+    pt, pl = int(padding[0]), int(padding[1])
+    Ho, Wo = out_hw if out_hw is not None else ((H + 2 * pt - 3) // stride + 1, (W + 2 * pl - 3) // stride + 1)
+    y = torch.empty(B, Cout, Ho, Wo, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if residual is not None:
+        residual = _nhwc(residual, "residual")
+        if residual.shape != y.shape:
+            raise ValueError("conv3x3_strided: residual shape mismatch")
+    with timed(f"conv3x3s{stride}|{B},{H},{W},{Cin},{Cout}"):
+        check(lib.ocv_conv3x3_nhwc_strided_fwd(x.data_ptr(), Cin, w_hi.data_ptr(), w_lo.data_ptr(), _ptr(bias), _ptr(residual),
+                                               y.data_ptr(), B, H, W, Cout, stride, pt, pl, Ho, Wo, act, _stream()),
+              "ocv_conv3x3_nhwc_strided_fwd")
+    return y
+
+
 __all__ = [_n for _n in dir() if not _n.startswith("__")]        # (private helpers included: the facade re-exports every name)

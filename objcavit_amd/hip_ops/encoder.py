@@ -45,6 +45,17 @@ def depthwise_conv_same(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     return out
 
 
+def _out_pad(H: int, W: int, k: int, stride: int, padding: Optional[Tuple[int, int]]):
+    """(Ho, Wo, pad_t, pad_l) of a k x k / stride convolution: ``padding`` None = TensorFlow 'SAME' (the B family; the extra
+    row / column of an uneven pad goes to the bottom / right), else (pad_t, pad_l) passed straight through with symmetric
+    padding (torchvision's (k - 1) // 2: EfficientNetV2), Ho = (H + 2 pad_t - k) // stride + 1."""
+    if padding is None:
+        Ho, Wo = -(-H // stride), -(-W // stride)
+        return Ho, Wo, max((Ho - 1) * stride + k - H, 0) // 2, max((Wo - 1) * stride + k - W, 0) // 2
+    pt, pl = int(padding[0]), int(padding[1])
+    return (H + 2 * pt - k) // stride + 1, (W + 2 * pl - k) // stride + 1, pt, pl
+
+
 
 # ---------------------------------------------------------------------------
 # NHWC encoder blocks (pointwise conv with fused gate / bias / act / residual, depthwise, squeeze)
@@ -233,7 +244,7 @@ def depth_metrics(pred: torch.Tensor, gt: torch.Tensor, min_depth: float, max_de
 
 
 def stem_conv_same(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int,
-                   act: int = ACT_NONE) -> torch.Tensor:
+                   act: int = ACT_NONE, padding: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """Dense 3x3 convolution with TF 'SAME' padding of an NCHW image, + bias + act; returns a channels_last tensor.
     weight [Cout, Cin, 3, 3] with Cin * 9 <= 32, Cout <= 64."""
     lib = _lib.load()
@@ -247,13 +258,11 @@ def stem_conv_same(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
         _req(bias, "bias")
         if bias.numel() != Cout:
             raise ValueError("stem_conv_same: bias size mismatch")
-    Ho, Wo = -(-H // stride), -(-W // stride)
-    ph = max((Ho - 1) * stride + k - H, 0)
-    pw = max((Wo - 1) * stride + k - W, 0)
+    Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     out = torch.empty(B, Cout, Ho, Wo, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     with timed("stem_conv"):
         check(lib.ocv_stem_conv_fwd(x.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr(), B, Cin, H, W, Cout, k,
-                                    stride, ph // 2, pw // 2, Ho, Wo, act, _stream()), "ocv_stem_conv_fwd")
+                                    stride, pt, pl, Ho, Wo, act, _stream()), "ocv_stem_conv_fwd")
     return out
 
 
@@ -298,7 +307,7 @@ def depthwise_nhwc_same(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optiona
 
 
 def depthwise_se_gate(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[torch.Tensor], k: int, stride: int,
-                      w1: torch.Tensor, b1: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor):
+                      w1: torch.Tensor, b1: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor, padding: Optional[Tuple[int, int]] = None):
     """silu(depthwise k x k (TF 'SAME') + bias) of a channels_last tensor AND the squeeze-excite gate of that output: three
     launches (depthwise, hidden layer, gate; one for the last two where the squeeze-excite weights are small).
     Returns (y [B, C, Ho, Wo] channels_last, gate [B, C])."""
@@ -314,9 +323,7 @@ def depthwise_se_gate(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[
     R = w1.shape[0]
     if w1.shape != (R, Cc) or w2t.shape != (R, Cc) or b1.numel() != R or b2.numel() != Cc:
         raise ValueError("depthwise_se_gate: squeeze-excite parameter shape mismatch")
-    Ho, Wo = -(-H // stride), -(-W // stride)
-    ph = max((Ho - 1) * stride + k - H, 0)
-    pw = max((Wo - 1) * stride + k - W, 0)
+    Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     tiles = lib.ocv_depthwise_sum_tiles(B, Cc, Ho, Wo, k, stride)
     if tiles <= 0:
         raise ValueError("depthwise_se_gate: unsupported shape")
@@ -326,7 +333,7 @@ def depthwise_se_gate(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[
     hid = workspace(B * R * 4, x.device, "se_hidden")
     with timed(f"depthwise|{B},{H},{W},{Cc},k{k}s{stride}"):
         check(lib.ocv_depthwise_conv_nhwc_sum_fwd(x.data_ptr(), weight_kkc.data_ptr(), _ptr(bias), out.data_ptr(),
-                                                  part.data_ptr(), B, Cc, H, W, k, stride, ph // 2, pw // 2, Ho, Wo,
+                                                  part.data_ptr(), B, Cc, H, W, k, stride, pt, pl, Ho, Wo,
                                                   _stream()), "ocv_depthwise_conv_nhwc_sum_fwd")
     with timed("se_gate"):
         check(lib.ocv_se_gate_partials_fwd(part.data_ptr(), tiles, Ho * Wo, w1.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
@@ -337,7 +344,7 @@ def depthwise_se_gate(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[
 
 def depthwise_se_gate_weights(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[torch.Tensor], k: int, stride: int,
                               w1: torch.Tensor, b1: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor, w_proj: torch.Tensor,
-                              want_gate: bool = False):
+                              want_gate: bool = False, padding: Optional[Tuple[int, int]] = None):
     """silu(depthwise k x k (TF 'SAME') + bias) of a channels_last tensor written ONCE, in the hl32 split layout, and the
     squeeze-excite gate of that output FOLDED INTO the project weight per image: returns (y SplitAct [B, C, Ho, Wo],
     PerImageSplitWeight of w_proj [N, C] * diag(gate[b])) (+ the gate [B, C] with ``want_gate``).  Three launches."""
@@ -354,9 +361,7 @@ def depthwise_se_gate_weights(x: torch.Tensor, weight_kkc: torch.Tensor, bias: O
     N = w_proj.shape[0]
     if w1.shape != (R, Cc) or w2t.shape != (R, Cc) or b1.numel() != R or b2.numel() != Cc or tuple(w_proj.shape) != (N, Cc):
         raise ValueError("depthwise_se_gate_weights: parameter shape mismatch")
-    Ho, Wo = -(-H // stride), -(-W // stride)
-    ph = max((Ho - 1) * stride + k - H, 0)
-    pw = max((Wo - 1) * stride + k - W, 0)
+    Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     tiles = lib.ocv_depthwise_sum_tiles(B, Cc, Ho, Wo, k, stride)
     if tiles <= 0:
         raise ValueError("depthwise_se_gate_weights: unsupported shape")
@@ -368,7 +373,7 @@ def depthwise_se_gate_weights(x: torch.Tensor, weight_kkc: torch.Tensor, bias: O
     gate = torch.empty(B, Cc, dtype=torch.float32, device=x.device) if want_gate else None
     with timed(f"depthwise|{B},{H},{W},{Cc},k{k}s{stride}"):
         check(lib.ocv_depthwise_conv_nhwc_sum_hl_fwd(x.data_ptr(), weight_kkc.data_ptr(), _ptr(bias), None, ys.hl.data_ptr(),
-                                                     part.data_ptr(), B, Cc, H, W, k, stride, ph // 2, pw // 2, Ho, Wo,
+                                                     part.data_ptr(), B, Cc, H, W, k, stride, pt, pl, Ho, Wo,
                                                      _stream()), "ocv_depthwise_conv_nhwc_sum_hl_fwd")
     with timed("se_gate_weights"):
         check(lib.ocv_se_gate_weights_fwd(part.data_ptr(), tiles, Ho * Wo, w1.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
@@ -389,7 +394,7 @@ def expand_depthwise_fusable(cin: int, weight, k: int = 3) -> bool:
 
 def expand_depthwise_se_gate(x: torch.Tensor, w_expand: "SplitWeight", b_expand: Optional[torch.Tensor], weight_kkc: torch.Tensor,
                              bias: Optional[torch.Tensor], k: int, stride: int, w1: torch.Tensor, b1: torch.Tensor,
-                             w2t: torch.Tensor, b2: torch.Tensor):
+                             w2t: torch.Tensor, b2: torch.Tensor, padding: Optional[Tuple[int, int]] = None):
     """silu(depthwise(silu(x @ We^T + be)) + bd) of a channels_last tensor without materialising the expanded tensor, AND
     the squeeze-excite gate of that output: returns (y [B, mid, Ho, Wo] channels_last, gate [B, mid])."""
     lib = _lib.load()
@@ -410,9 +415,7 @@ def expand_depthwise_se_gate(x: torch.Tensor, w_expand: "SplitWeight", b_expand:
         raise ValueError("expand_depthwise_se_gate: squeeze-excite parameter shape mismatch")
     if (b_expand is not None and b_expand.numel() != mid) or (bias is not None and bias.numel() != mid):
         raise ValueError("expand_depthwise_se_gate: bias size mismatch")
-    Ho, Wo = -(-H // stride), -(-W // stride)
-    ph = max((Ho - 1) * stride + k - H, 0)
-    pw = max((Wo - 1) * stride + k - W, 0)
+    Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     tiles = lib.ocv_mbconv_expand_dw_tiles(Ho, Wo, k, stride)
     if tiles <= 0:
         raise ValueError("expand_depthwise_se_gate: unsupported shape")
@@ -423,7 +426,7 @@ def expand_depthwise_se_gate(x: torch.Tensor, w_expand: "SplitWeight", b_expand:
     with timed(f"expand_dw|{B},{H},{W},{Cin},{mid},k{k}s{stride}"):
         check(lib.ocv_mbconv_expand_dw_fwd(x.data_ptr(), w_expand.packed.data_ptr(), _ptr(b_expand), weight_kkc.data_ptr(),
                                            _ptr(bias), out.data_ptr(), part.data_ptr(), B, H, W, Cin, mid, k, stride,
-                                           ph // 2, pw // 2, Ho, Wo, _stream()), "ocv_mbconv_expand_dw_fwd")
+                                           pt, pl, Ho, Wo, _stream()), "ocv_mbconv_expand_dw_fwd")
     with timed("se_gate"):
         check(lib.ocv_se_gate_partials_fwd(part.data_ptr(), tiles, Ho * Wo, w1.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
                                            b2.data_ptr(), gate.data_ptr(), hid.data_ptr(), B, mid, R, _stream()),

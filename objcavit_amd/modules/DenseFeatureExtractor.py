@@ -25,7 +25,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import hip_ops
-from .efficientnet import tf_efficientnet_b5_ap
+from .efficientnet import tf_efficientnet_b1_ap, tf_efficientnet_b5_ap
+from .efficientnet_v2 import efficientnet_v2_m, efficientnet_v2_s
 
 
 def split_bf16_convs_enabled() -> bool:
@@ -718,10 +719,27 @@ class Decoder(nn.Module):
         return self.conv3(x)
 
 
+def _backbone_for(name: str) -> nn.Module:
+    """The backbone of an encoder name, as the reference picks it (reference :141-166): B5 / B1 in the gen-efficientnet
+    layout, V2-S / V2-M in torchvision's.  Unknown names exit, as the reference's Decoder does."""
+    if "efficientnet-b5" in name:
+        return tf_efficientnet_b5_ap(pretrained=False)
+    if "efficientnet-b1" in name:
+        return tf_efficientnet_b1_ap(pretrained=False)
+    if "efficientnet-v2-s" in name:
+        return efficientnet_v2_s()
+    if "efficientnet-v2-m" in name:
+        return efficientnet_v2_m()
+    sys.exit(f"Error: encoder '{name}' is not available in this build "
+             "(efficientnet-b5, efficientnet-b1, efficientnet-v2-s, efficientnet-v2-m).")
+
+
 class DenseFeatureExtractor(nn.Module):
-    """``args`` is the reference's config tree (see objcavit_amd.config).  Only
-    the EfficientNet-B5 backbone is available locally; the reference's other
-    encoder choices need torchvision / hub downloads (reference :141-168)."""
+    """``args`` is the reference's config tree (see objcavit_amd.config).  The
+    reference's four encoders are local modules without weights (reference
+    :141-168): efficientnet-b5 and -b1 (gen-efficientnet layout, num_features
+    2048 / 1280) and efficientnet-v2-s / -v2-m (torchvision layout,
+    num_features 1280); load weights from a checkpoint."""
 
     def __init__(self, args, backbone: Optional[nn.Module] = None):
         super().__init__()
@@ -735,14 +753,17 @@ class DenseFeatureExtractor(nn.Module):
 
         name = block.encoder_name
         if backbone is None:
-            if "efficientnet-b5" not in name:
-                sys.exit(f"Error: encoder '{name}' is not available in this build (efficientnet-b5 only).")
-            backbone = tf_efficientnet_b5_ap(pretrained=False)
-        # remove unused final layers, as the reference does (:152-156)
-        backbone.bn2 = nn.Identity()
-        backbone.act2 = nn.Identity()
-        backbone.global_pool = nn.Identity()
-        backbone.classifier = nn.Identity()
+            backbone = _backbone_for(name)
+        if "efficientnet-v2-" in name:
+            # the V2 head (1x1 conv, BN, SiLU) stays in ``features``; only pooling and classifier go (reference :164-166)
+            backbone.avgpool = nn.Identity()
+            backbone.classifier = nn.Identity()
+        else:
+            # remove unused final layers, as the reference does (:152-156)
+            backbone.bn2 = nn.Identity()
+            backbone.act2 = nn.Identity()
+            backbone.global_pool = nn.Identity()
+            backbone.classifier = nn.Identity()
         num_features = 2048 if "efficientnet-b5" in name else 1280
 
         self.decoder = Decoder(num_classes=128, num_features=num_features, bottleneck_features=num_features,

@@ -41,6 +41,10 @@ BN_MOMENTUM = 0.01
 B5_STAGES = (("ds", 3, 3, 1, 1, 24), ("ir", 5, 3, 2, 6, 40), ("ir", 5, 5, 2, 6, 64), ("ir", 7, 3, 2, 6, 128),
              ("ir", 7, 5, 1, 6, 176), ("ir", 9, 5, 2, 6, 304), ("ir", 3, 3, 1, 6, 512))
 B5_STEM, B5_HEAD = 48, 2048
+# tf_efficientnet_b1_ap: width x1.0, depth x1.1 (23 blocks), same kernels / strides / expansions
+B1_STAGES = (("ds", 2, 3, 1, 1, 16), ("ir", 3, 3, 2, 6, 24), ("ir", 3, 5, 2, 6, 40), ("ir", 4, 3, 2, 6, 80),
+             ("ir", 4, 5, 1, 6, 112), ("ir", 5, 5, 2, 6, 192), ("ir", 2, 3, 1, 6, 320))
+B1_STEM, B1_HEAD = 32, 1280
 
 
 class Conv2dSame(nn.Conv2d):
@@ -263,3 +267,9 @@ def tf_efficientnet_b5_ap(pretrained: bool = False) -> GenEfficientNet:
     There is no network here: ``pretrained`` weights must be loaded by the
     caller from a state_dict / checkpoint."""
     return GenEfficientNet()
+
+
+def tf_efficientnet_b1_ap(pretrained: bool = False) -> GenEfficientNet:
+    """EfficientNet-B1 in the same layout (stem 32, head 1280, B1_STAGES; 7,794,184 parameters with the classifier).
+    No weights: see tf_efficientnet_b5_ap."""
+    return GenEfficientNet(B1_STAGES, B1_STEM, B1_HEAD)
