@@ -63,3 +63,15 @@ def golden_sample_dev(x, z, t, images=None):
     samp = float((got - val).abs().max()) / den
     mom = max(float((got_mean - mean).abs().max()), float((got_rms - rms).abs().max())) / den
     return samp, mom
+
+
+def branch_dev(y, ref, x=None):
+    """Per image (dim 0) of a block's output ``y`` against its float64 reference ``ref``: max |y - ref| / max |ref - x| for a
+    residual block with input ``x`` -- relative to the residual branch rather than the stream it is added to -- and
+    max |y - ref| / max |ref| without ``x``.  Returns a list of floats, one per image."""
+    y = torch.as_tensor(y).detach().cpu().double()
+    ref = torch.as_tensor(ref).detach().cpu().double()
+    assert y.shape == ref.shape, (y.shape, ref.shape)
+    den = ref if x is None else ref - torch.as_tensor(x).detach().cpu().double()
+    num = (y - ref).flatten(1).abs().amax(1)
+    return (num / (den.flatten(1).abs().amax(1) + 1e-30)).tolist()
