@@ -1,4 +1,4 @@
-// Implicit-GEMM convolution (k = 1 or 3, stride 1, "same" zero padding) on
+// Implicit-GEMM convolution (k = 1 or 3, stride 1 or 2, zero padding) on
 // NHWC fp32 activations for gfx950, computed on the bf16 matrix cores with
 // SPLIT-bf16 operands and fp32 accumulation:
 //
@@ -16,12 +16,17 @@
 // (modules/DenseFeatureExtractor.py:37-42,97,104-116) and MIOpen's fp32
 // implicit GEMM already sits at 85 % of the fp32 matrix peak there.
 //
-// GEMM view: M = B*H*W output pixels, N = Cout, K = taps x Cin.  The A operand
-// is gathered on the fly (tap offset, zero outside the image) from one or two
-// NHWC tensors -- a second tensor acts as a virtual channel concat, which is how
-// UpSampleWithSkip feeds [upsampled, skip] without materialising the cat --
-// and split into hi/lo in registers on its way to LDS.  Weights are split once
-// on the host into two bf16 arrays laid out [tap][Cout][Cin rounded up to 32].
+// GEMM view: M = B*Ho*Wo output pixels, N = Cout, K = taps x Cin.  Output
+// pixel (b, oy, ox) reads input pixel (b, S oy - pad_t + ky, S ox - pad_l + kx)
+// at tap (ky, kx), zero outside the image: stride 1 with pad = k / 2 and
+// Ho, Wo = H, W is the decoder's "same" convolution (ocv_conv_nhwc_fwd); stride
+// 1 or 2 with explicit top / left padding and output size is EfficientNetV2's
+// Fused-MBConv 3x3 (ocv_conv3x3_nhwc_strided_fwd).  The A operand is gathered
+// on the fly from one or two NHWC tensors -- a second tensor acts as a virtual
+// channel concat, which is how UpSampleWithSkip feeds [upsampled, skip] without
+// materialising the cat -- and split into hi/lo in registers on its way to LDS.
+// Weights are split once on the host into two bf16 arrays laid out
+// [tap][Cout][Cin rounded up to 32].
 //
 // Tile: 256 pixels x 128 channels per workgroup; K advances 32 channels of one tap per step (channel chunk outer,
 // tap inner: the nine taps of a chunk re-read the same L2-resident lines) through a double-buffered LDS image
@@ -37,8 +42,8 @@
 //              selects), split it into hi/lo, fetch the pre-split weight chunk, write the other LDS buffer.
 // One consumer and one producer wave share each SIMD: matrix pipe and VALU run side by side; one barrier per step.
 // Workgroup ids are remapped so that the N-tiles of one pixel tile run on the same XCD and share its L2.
-// conv_strided.hip holds a copy of conv_igemm_kernel's schedule (tile map, consumer loop, two producer groups) with a strided
-// gather (stride 1 / 2, explicit padding: EfficientNetV2's Fused-MBConv): a fix to the schedule here belongs there too.
+// Kernel size, stride and the second source are template parameters (conv_igemm_kernel<KS, S, CAT>): the tap loop, the
+// tap -> (ky, kx) split and the source select are resolved at compile time.
 #include <stdlib.h>
 
 #include "common.hpp"
@@ -64,6 +69,7 @@ struct ConvArgs {
   const __bf16* whi; const __bf16* wlo; // [taps][Cout][Cp]
   const float* bias; const float* res; float* y;
   int C1, C2, Cin, Cp, Cout, H, W, ks, act;
+  int Ho, Wo, pad_t, pad_l;             // conv_igemm_kernel: output size, zero padding on top / left (its stride is a template parameter)
   long M;
   int mtiles, ntiles;
   int ksplit;                           // conv_split_dma_kernel: 1, or 2 = the channel chunks are halved between two workgroups
@@ -164,7 +170,8 @@ __device__ __forceinline__ long hl_index(long m, int c, int Cp) { return m * 2 *
 __device__ __attribute__((aligned(256))) float ocv_zero_page[64];      // zero-initialised: source of padded taps
 
 
-template <bool IN_SPLIT>   /* always false: pre-split inputs take conv_split_dma_kernel */
+// KS: kernel size (1 or 3); S: stride (1 or 2); CAT: x2 is concatenated after x1's channels
+template <int KS, int S, bool CAT>
 __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
@@ -181,7 +188,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   const int mt = wg / p.ntiles, nt = wg - mt * p.ntiles;
   const long m0 = (long)mt * CBM;
   const int n0 = nt * CBN;
-  const int taps = p.ks * p.ks, pad = p.ks >> 1;
+  constexpr int taps = KS * KS;
   const int nsteps = taps * (p.Cp / CBK);
 
   if (wave < 4) {
@@ -244,12 +251,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
             else if (p.act == OCV_ACT_SILU) v = fast_silu(v);
             else if (p.act == OCV_ACT_RELU) v = fmaxf(v, 0.f);
             if (p.res != nullptr) v += p.res[m * p.Cout + n];
-            if (p.y != nullptr) p.y[m * p.Cout + n] = v;
-            if (p.yhl != nullptr) {                      // pre-split copy for the next convolution's A operand
-              const __bf16 hb = (__bf16)v;
-              p.yhl[hl_index(m, n, p.Cpo)] = hb;
-              p.yhl[hl_index(m, n, p.Cpo) + 32] = (__bf16)(v - (float)hb);
-            }
+            p.y[m * p.Cout + n] = v;
           }
         }
     }
@@ -268,31 +270,36 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   // flight and all loads are ordinary, compiler-visible loads (see gload16): exact s_waitcnt, no stale registers.
   //
   // All per-lane address work is hoisted out of the K loop (s_memtime stamps showed 2200 of 3600 producer cycles per
-  // step in 64-bit index arithmetic, divisions and bounds tests): per row the byte offsets of the pixel in both source
-  // tensors (32-bit; operands < 4 GiB, checked on the host) and a 9-bit mask of in-image taps; per step one scalar
-  // byte offset for (tap shift, channel chunk); tap / chunk counters advance incrementally.
+  // step in 64-bit index arithmetic, divisions and bounds tests): per row the byte offsets of its window's top-left
+  // input pixel in both source tensors and a 9-bit mask of in-image taps; per step one scalar, non-negative byte offset
+  // for (tap, channel chunk); tap / chunk counters advance incrementally.  The row offsets are 32-bit and may wrap below
+  // zero when the corner lies in the padding: they are only ever added to the offset of an in-image tap, and that sum
+  // lies inside the operand (< 4 GiB, checked on the host).
   const int g = (wave - 4) >> 1;                       // producer group
   const int gt = tid - 256 - 128 * g;                  // 0..127 inside the group
   // A role: 4 lanes per row (32 B = 8 channels each); rows (gt >> 2) + 32 i, i = 0..7
   const int apart = (gt & 3) * 8;
-  unsigned rb1[8], rb2[8], tapmask[8];
+  unsigned rb1[8], rb2[8], tapmask[8];                  // rb2: only with CAT
   {
-    const long hw = (long)p.H * p.W;
+    const long hw = (long)p.Ho * p.Wo;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const long am = m0 + (gt >> 2) + 32 * i;
       const bool valid = am < p.M;
-      const long rem = valid ? am % hw : 0;
-      const int y = (int)(rem / p.W), x = (int)(rem - (long)y * p.W);
+      const long pix = valid ? am : 0;
+      const long b = pix / hw, rem = pix - b * hw;
+      const int oy = (int)(rem / p.Wo), ox = (int)(rem - (long)oy * p.Wo);
+      const int iy0 = oy * S - p.pad_t, ix0 = ox * S - p.pad_l;
       unsigned mask = 0;
+#pragma unroll
       for (int t = 0; t < taps; ++t) {
-        const int dy = t / p.ks - pad, dx = t % p.ks - pad;
-        if (valid && (unsigned)(y + dy) < (unsigned)p.H && (unsigned)(x + dx) < (unsigned)p.W) mask |= 1u << t;
+        const int iy = iy0 + t / KS, ix = ix0 + t % KS;
+        if (valid && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) mask |= 1u << t;
       }
       tapmask[i] = mask;
-      const long pix = valid ? am : 0;
-      rb1[i] = IN_SPLIT ? (unsigned)((pix * 2 * p.Cp + apart) * 2) : (unsigned)((pix * p.C1 + apart) * 4);
-      rb2[i] = (unsigned)((pix * p.C2 + apart) * 4);
+      const long corner = (b * p.H + iy0) * p.W + ix0;
+      rb1[i] = (unsigned)((corner * p.C1 + apart) * 4);
+      if (CAT) rb2[i] = (unsigned)((corner * p.C2 + apart) * 4);
     }
   }
   // B role: one weight row per lane (32 channels: 64 B of hi, 64 B of lo)
@@ -312,32 +319,19 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   auto issue_loads = [&](Raw& st) {
     const int tap = nx_tap, c0 = nx_c0;
     advance();
-    const int ky = tap / p.ks, kx = tap - ky * p.ks;                     // scalar, ks in {1, 3}
-    if (IN_SPLIT) {
-      // pre-split input: 8 channels = 16 B of hi and 16 B of lo per lane and row, no conversion later
-      const int soff = (((ky - pad) * p.W + (kx - pad)) * 2 * p.Cp + 2 * c0) * 2;      // hl32: chunk c0 starts at 2 c0
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool ok = ((tapmask[i] >> tap) & 1u);
-        const unsigned off = rb1[i] + (unsigned)soff;
-        st.a[2 * i + 0] = gload16(ok ? (const void*)((const char*)p.xhl + off) : (const void*)ocv_zero_page);
-        st.a[2 * i + 1] = gload16(ok ? (const void*)((const char*)p.xhl + off + 64) : (const void*)ocv_zero_page);
-      }
-    } else {
-    const bool first = c0 < p.C1;
+    const int ky = tap / KS, kx = tap - ky * KS;
+    const bool first = !CAT || c0 < p.C1;
     const char* tbase = (const char*)(first ? p.x1 : p.x2);
     const int tc = first ? p.C1 : p.C2;
     const int cin = first ? c0 : c0 - p.C1;                              // chunk start inside the source tensor
-    const int soff = (((ky - pad) * p.W + (kx - pad)) * tc + cin) * 4;   // scalar byte offset of (tap, chunk)
+    const unsigned soff = (unsigned)(((ky * p.W + kx) * tc + cin) * 4);  // scalar byte offset of (tap, chunk)
     const bool cok0 = cin + apart + 4 <= tc, cok1 = cin + apart + 8 <= tc;   // channel tail of a partial chunk
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const bool inb = (tapmask[i] >> tap) & 1u;
-      const unsigned off = (first ? rb1[i] : rb2[i]) + (unsigned)soff;
-      const char* src = tbase + off;
+      const char* src = tbase + ((first ? rb1[i] : rb2[i]) + soff);
       st.a[2 * i + 0] = gload16((inb && cok0) ? (const void*)src : (const void*)ocv_zero_page);
       st.a[2 * i + 1] = gload16((inb && cok1) ? (const void*)(src + 16) : (const void*)ocv_zero_page);
-    }
     }
     const unsigned woff = (unsigned)tap * wtap + wrow + (unsigned)c0 * 2;
 #pragma unroll
@@ -349,11 +343,6 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   auto convert = [&](const Raw& st, Cvt& cv) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      if (IN_SPLIT) {
-        cv.ahi[i] = __builtin_bit_cast(bf16x8, st.a[2 * i + 0]);
-        cv.alo[i] = __builtin_bit_cast(bf16x8, st.a[2 * i + 1]);
-        continue;
-      }
       __bf16 hi[8], lo[8];
       split4(st.a[2 * i + 0], hi, lo);
       split4(st.a[2 * i + 1], hi + 4, lo + 4);
@@ -835,31 +824,41 @@ int conv_ksplit(long M, int Cout, int Cin, int ksize) {
   const double c1 = (double)((tiles + 255) / 256), c2 = (double)((2 * tiles + 255) / 256) / 2.0;
   return c2 <= 0.9 * c1 ? 2 : 1;
 }
-int launch_conv(ConvArgs& a, int B, bool in_split, hipStream_t st) {
+// conv_split_dma_kernel (pre-split input)
+int launch_conv(ConvArgs& a, int B, hipStream_t st) {
   a.Cp = (a.Cin + CBK - 1) / CBK * CBK;
   a.M = (long)B * a.H * a.W;
   a.mtiles = ocv_cdiv(a.M, CBM); a.ntiles = ocv_cdiv(a.Cout, CBN);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv_split_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv_split_dma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  if (in_split) {
-    static bool attr2 = false;
-    if (!attr2) {
-      (void)hipFuncSetAttribute((const void*)conv_split_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_split_dma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr2 = true;
-    }
-    if (a.ksplit < 1) a.ksplit = 1;
-    if (a.zbatch < 1) a.zbatch = 1;
-    const unsigned parts = a.zflat > 0 ? a.zflat : a.ksplit * a.zbatch;
-    if (a.f16)
-      hipLaunchKernelGGL(conv_split_dma_kernel<true>, dim3(a.mtiles * a.ntiles * parts), dim3(512), DNBUF * DBUF, st, a);
-    else
-      hipLaunchKernelGGL(conv_split_dma_kernel<false>, dim3(a.mtiles * a.ntiles * parts), dim3(512), DNBUF * DBUF, st, a);
-  } else hipLaunchKernelGGL(conv_igemm_kernel<false>, dim3(a.mtiles * a.ntiles), dim3(512), 2 * BUF_BYTES, st, a);
+  if (a.ksplit < 1) a.ksplit = 1;
+  if (a.zbatch < 1) a.zbatch = 1;
+  const unsigned parts = a.zflat > 0 ? a.zflat : a.ksplit * a.zbatch;
+  if (a.f16)
+    hipLaunchKernelGGL(conv_split_dma_kernel<true>, dim3(a.mtiles * a.ntiles * parts), dim3(512), DNBUF * DBUF, st, a);
+  else
+    hipLaunchKernelGGL(conv_split_dma_kernel<false>, dim3(a.mtiles * a.ntiles * parts), dim3(512), DNBUF * DBUF, st, a);
   OCV_CHECK_LAUNCH("ocv_conv_nhwc");
+  return 0;
+}
+
+// conv_igemm_kernel (fp32 input) over the output grid B x Ho x Wo
+template <int KS, int S, bool CAT>
+int launch_igemm(ConvArgs& a, int B, hipStream_t st, const char* name) {
+  a.Cp = (a.Cin + CBK - 1) / CBK * CBK;
+  a.M = (long)B * a.Ho * a.Wo;
+  a.mtiles = ocv_cdiv(a.M, CBM); a.ntiles = ocv_cdiv(a.Cout, CBN);
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<KS, S, CAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  hipLaunchKernelGGL((conv_igemm_kernel<KS, S, CAT>), dim3(a.mtiles * a.ntiles), dim3(512), 2 * BUF_BYTES, st, a);
+  OCV_CHECK_LAUNCH(name);
   return 0;
 }
 }  // namespace
@@ -904,14 +903,14 @@ extern "C" int ocv_conv_nhwc_split_x_fwd(const void* x_hl, int Cin, const void* 
     // two workgroups per tile, each over half of the channel chunks -> raw partial sums -> finish pass
     ConvArgs h = a;
     h.bias = nullptr; h.res = nullptr; h.yhl = nullptr; h.act = OCV_ACT_NONE; h.y = (float*)workspace; h.ksplit = ks; h.oscale = nullptr;
-    const int rc = launch_conv(h, B, true, (hipStream_t)stream);
+    const int rc = launch_conv(h, B, (hipStream_t)stream);
     if (rc != 0) return rc;
     FinArgs f{(const float*)workspace, bias, residual, y, (__bf16*)y_hl, M, M * Cout / 8, Cout, a.Cpo, act, ks, oscale, f16, a.range_flag};
     hipLaunchKernelGGL(conv_splitk_finish_kernel, dim3((unsigned)((f.items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f);
     OCV_CHECK_LAUNCH("ocv_conv_nhwc_split_fwd(finish)");
     return 0;
   }
-  return launch_conv(a, B, true, (hipStream_t)stream);
+  return launch_conv(a, B, (hipStream_t)stream);
 }
 
 // PACKED TAPS (round 6; ConvArgs::gpt): the same 3 x 3 convolution with the K axis = the nine taps' REAL 8-channel granules laid end
@@ -953,7 +952,7 @@ extern "C" int ocv_conv3x3_split_packed_taps_fwd(const void* x_hl, int Cin, cons
     const int zrc = ocv_zero_async(y_hl, ocv_split_act_elems(B, H, W, Cout) * sizeof(__bf16), (hipStream_t)stream);
     if (zrc != 0) return zrc;
   }
-  return launch_conv(a, B, true, (hipStream_t)stream);
+  return launch_conv(a, B, (hipStream_t)stream);
 }
 
 extern "C" int ocv_conv_nhwc_split_ws_fwd(const void* x_hl, int Cin, const void* w_hi, const void* w_lo, const float* bias,
@@ -987,8 +986,36 @@ extern "C" int ocv_conv_nhwc_fwd(const float* x1, int C1, const float* x2, int C
   a.x1 = x1; a.x2 = x2; a.whi = (const __bf16*)w_hi; a.wlo = (const __bf16*)w_lo;
   a.bias = bias; a.res = residual; a.y = y;
   a.C1 = C1; a.C2 = x2 ? C2 : 0; a.Cin = a.C1 + a.C2;
-  a.Cout = Cout; a.H = H; a.W = W; a.ks = ksize; a.act = act;
-  return launch_conv(a, B, false, (hipStream_t)stream);
+  a.Cout = Cout; a.H = H; a.W = W; a.act = act;
+  a.Ho = H; a.Wo = W; a.pad_t = a.pad_l = ksize / 2;                  // stride 1, "same"
+  const hipStream_t st = (hipStream_t)stream;
+  if (ksize == 1) return x2 ? launch_igemm<1, 1, true>(a, B, st, "ocv_conv_nhwc") : launch_igemm<1, 1, false>(a, B, st, "ocv_conv_nhwc");
+  return x2 ? launch_igemm<3, 1, true>(a, B, st, "ocv_conv_nhwc") : launch_igemm<3, 1, false>(a, B, st, "ocv_conv_nhwc");
+}
+
+extern "C" int ocv_conv3x3_nhwc_strided_fwd(const float* x, int Cin, const void* w_hi, const void* w_lo, const float* bias,
+                                            const float* residual, float* y, int B, int H, int W, int Cout, int stride,
+                                            int pad_t, int pad_l, int Ho, int Wo, int act, ocv_stream_t stream) {
+  OCV_CHECK_ARG(x && w_hi && w_lo && y, "ocv_conv3x3_nhwc_strided_fwd: null pointer");
+  OCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1 && Cout >= 1 && Cin >= 4 && Cin % 4 == 0,
+                "ocv_conv3x3_nhwc_strided_fwd: bad sizes (Cin must be a positive multiple of 4)");
+  OCV_CHECK_ARG(stride == 1 || stride == 2, "ocv_conv3x3_nhwc_strided_fwd: stride must be 1 or 2 (got %d)", stride);
+  OCV_CHECK_ARG(pad_t >= 0 && pad_l >= 0 && pad_t < 3 && pad_l < 3, "ocv_conv3x3_nhwc_strided_fwd: bad padding (%d, %d)", pad_t, pad_l);
+  OCV_CHECK_ARG((Ho - 1) * stride - pad_t < H && (Wo - 1) * stride - pad_l < W,
+                "ocv_conv3x3_nhwc_strided_fwd: output larger than the padded input allows");
+  OCV_CHECK_ARG(act >= 0 && act <= 3, "ocv_conv3x3_nhwc_strided_fwd: unknown activation %d", act);
+  OCV_CHECK_ARG(ocv_aligned16(x) && ocv_aligned16(w_hi) && ocv_aligned16(w_lo),
+                "ocv_conv3x3_nhwc_strided_fwd: operands must be 16-byte aligned");
+  OCV_CHECK_ARG((long)B * H * W * Cin * 4 < (1L << 31) && 9L * Cout * (Cin + 32) * 2 < (1L << 31),
+                "ocv_conv3x3_nhwc_strided_fwd: each operand must be smaller than 2 GiB (32-bit byte offsets inside the kernel)");
+  ConvArgs a{};
+  a.x1 = x; a.whi = (const __bf16*)w_hi; a.wlo = (const __bf16*)w_lo;
+  a.bias = bias; a.res = residual; a.y = y;
+  a.C1 = Cin; a.Cin = Cin; a.Cout = Cout;
+  a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.pad_t = pad_t; a.pad_l = pad_l; a.act = act;
+  const hipStream_t st = (hipStream_t)stream;
+  if (stride == 1) return launch_igemm<3, 1, false>(a, B, st, "ocv_conv3x3_nhwc_strided_fwd");
+  return launch_igemm<3, 2, false>(a, B, st, "ocv_conv3x3_nhwc_strided_fwd");
 }
 
 namespace {
@@ -1320,7 +1347,7 @@ extern "C" int ocv_conv3x3_winograd43_split_fwd(const void* x_hl, int Cin, const
   a.zbatch = 36; a.xz_bytes = T * 2 * Cp * (long)sizeof(_Float16); a.wz_bytes = (long)Cout * Cp * (long)sizeof(_Float16);
   a.Cpo = (Cout + 31) / 32 * 32;
   a.f16 = 1;
-  const int rc = launch_conv(a, 1, true, st);
+  const int rc = launch_conv(a, 1, st);
   if (rc != 0) return rc;
   Wino43OutArgs wo{m, fscale, tinv, bias, y, (__bf16*)y_hl, B, H, W, Cout, a.Cpo, th, tw, act, T, T * (Cout / 4), hl_f16,
                    (hl_f16 && y_hl != nullptr) ? ocv_range_flag_current() : nullptr};
@@ -1429,7 +1456,7 @@ extern "C" int ocv_patch_embed_split_fwd(const void* x_hl, int C, const void* w_
   a.rowpitch = (unsigned)(16L * w * 2 * C * (long)sizeof(__bf16));           // grid rows: 16 image rows apart
   // image b's rows start at image row b h, not b gh 16, when h is not a multiple of 16: only then is the grid not uniform
   OCV_CHECK_ARG(h % 16 == 0 || B == 1, "ocv_patch_embed_split_fwd: the map height must be a multiple of 16 for B > 1 (got %d)", h);
-  const int rc = launch_conv(a, 1, true, (hipStream_t)stream);
+  const int rc = launch_conv(a, 1, (hipStream_t)stream);
   if (rc != 0) return rc;
   const long M = (long)B * gh * gw;
   hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)((M * (E / 4) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,

@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import hip_ops
-from .efficientnet import tf_efficientnet_b1_ap, tf_efficientnet_b5_ap
+from .efficientnet import fold_bn, tf_efficientnet_b1_ap, tf_efficientnet_b5_ap
 from .efficientnet_v2 import efficientnet_v2_m, efficientnet_v2_s
 
 
@@ -112,7 +112,7 @@ class SplitConv3x3:
                 raise RuntimeError("weight preparation during graph capture: run one eager warm-up call first")
             with torch.no_grad():
                 if self.bn is not None:
-                    w, b = _fold_conv_bn(self.conv, self.bn)
+                    w, b = fold_bn(self.conv, self.bn)
                 else:
                     w, b = self.conv.weight, self.conv.bias
                 k = w.shape[-1]
@@ -241,43 +241,33 @@ class Encoder(nn.Module):
                 push(child(cur))
         return feats
 
-
-def _encoder_fused_stem(self, x, push):
-    """conv_stem + bn1 + act1 as ONE launch (csrc/stem.hip) on the inference fast path, when the caller does not keep
-    the two intermediate activations.  Returns the child names that were consumed."""
-    m = self.original_model
-    names = list(m._modules)[:3]
-    if names != ["conv_stem", "bn1", "act1"] or self.keep is None or 1 in self.keep or 2 in self.keep:
-        return ()
-    conv, bn, act = m.conv_stem, m.bn1, m.act1
-    if not (x.device.type == "cuda" and not torch.is_grad_enabled() and not m.training and isinstance(conv, nn.Conv2d)
-            and isinstance(bn, nn.BatchNorm2d) and isinstance(act, nn.SiLU) and conv.kernel_size == (3, 3)
-            and conv.groups == 1 and conv.in_channels * 9 <= 32 and conv.out_channels <= 64
-            and conv.padding == (0, 0) and conv.stride[0] == conv.stride[1] and x.dtype == torch.float32):
-        return ()
-    key = (x.device, conv.weight._version, conv.weight.data_ptr(), bn.weight._version, bn.bias._version,
-           bn.running_mean._version, bn.running_var._version)
-    c = self.__dict__.get("_stem_cache")
-    if c is None or c[0] != key:
-        with torch.no_grad():
-            w, b = _fold_conv_bn(conv, bn)
-            c = (key, w.float().contiguous(), b.float().contiguous())
-        self.__dict__["_stem_cache"] = c
-    y = hip_ops.stem_conv_same(x.contiguous(), c[1], c[2], conv.stride[0], hip_ops.ACT_SILU)
-    push(None)
-    push(None)
-    push(y)
-    return ("conv_stem", "bn1", "act1")
-
-
-Encoder._fused_stem = _encoder_fused_stem
-
-
-def _fold_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
-    s = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-    w = conv.weight * s.view(-1, 1, 1, 1)
-    b0 = conv.bias if conv.bias is not None else torch.zeros_like(bn.running_mean)
-    return w, (b0 - bn.running_mean) * s + bn.bias
+    def _fused_stem(self, x, push):
+        """conv_stem + bn1 + act1 as ONE launch (csrc/stem.hip) on the inference fast path, when the caller does not keep
+        the two intermediate activations.  Returns the child names that were consumed."""
+        m = self.original_model
+        names = list(m._modules)[:3]
+        if names != ["conv_stem", "bn1", "act1"] or self.keep is None or 1 in self.keep or 2 in self.keep:
+            return ()
+        conv, bn, act = m.conv_stem, m.bn1, m.act1
+        if not (x.device.type == "cuda" and not torch.is_grad_enabled() and not m.training and isinstance(conv, nn.Conv2d)
+                and isinstance(bn, nn.BatchNorm2d) and isinstance(act, nn.SiLU) and conv.kernel_size == (3, 3)
+                and conv.groups == 1 and conv.in_channels * 9 <= 32 and conv.out_channels <= 64
+                and conv.padding == (0, 0) and conv.stride[0] == conv.stride[1] and x.dtype == torch.float32):
+            return ()
+        # identity and version of every tensor the fold reads (as _FoldedMixin._fold_key)
+        ts = [t for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+        key = (x.device,) + tuple((t.data_ptr(), t._version) for t in ts)
+        c = self.__dict__.get("_stem_cache")
+        if c is None or c[0] != key:
+            with torch.no_grad():
+                w, b = fold_bn(conv, bn)
+                c = (key, w.float().contiguous(), b.float().contiguous())
+            self.__dict__["_stem_cache"] = c
+        y = hip_ops.stem_conv_same(x.contiguous(), c[1], c[2], conv.stride[0], hip_ops.ACT_SILU)
+        push(None)
+        push(None)
+        push(y)
+        return ("conv_stem", "bn1", "act1")
 
 
 class _ShapeOnly:
@@ -441,7 +431,7 @@ class UpSampleWithSkip(nn.Module):
         # CPU, eval: plain PyTorch with folded BatchNorm (what the golden generator wraps; never the GPU path)
         if self._folded is None or self._folded[0].device != f.device:
             with torch.no_grad():
-                self._folded = (*_fold_conv_bn(self._net[0], self._net[1]), *_fold_conv_bn(self._net[3], self._net[4]))
+                self._folded = (*fold_bn(self._net[0], self._net[1]), *fold_bn(self._net[3], self._net[4]))
         w1, b1, w2, b2 = self._folded
         f = F.leaky_relu(F.conv2d(f, w1, b1, padding=1), 0.01)
         return F.leaky_relu(F.conv2d(f, w2, b2, padding=1), 0.01)

@@ -207,31 +207,36 @@ class InvertedResidual(_FoldedMixin, nn.Module):
 
     def forward(self, x):
         if self._fast(x):
-            # NHWC plan, 4 launches: expand 1x1 (+BN+SiLU) -> depthwise (+BN+SiLU, + pooling partials) -> gate ->
-            # project 1x1 (+BN) with the gate applied to its input rows and the skip connection added in the epilogue
-            we, be, wd, bd, wl, bl, s1, sb1, s2, sb2, wl_f32 = self._folded(x)
-            k, stride = self.conv_dw.kernel_size[0], self.conv_dw.stride[0]
-            B, cin, H, W = x.shape
-            mid, cout = self.conv_pw.out_channels, self.conv_pwl.out_channels
-            Ho, Wo = -(-H // stride), -(-W // stride)
-            split_w = isinstance(we, hip_ops.SplitWeight)
-            res = x if self.has_residual else None
-            if hip_ops.expand_depthwise_fusable(cin, we, k):
-                # 3 launches: the expanded tensor stays in LDS (csrc/mbconv_fused.hip)
-                y, g = hip_ops.expand_depthwise_se_gate(x, we, be, wd, bd, k, stride, s1, sb1, s2, sb2)
-                return hip_ops.pointwise_nhwc(y, wl, bl, hip_ops.ACT_NONE, gate=g, residual=res)
-            y = hip_ops.pointwise_nhwc(x, we, be, hip_ops.ACT_SILU)
-            if split_w and hip_ops.pointwise_hl_project_pays(B, Ho * Wo, mid, cout):
-                # stage 5's projects (long K, weights well under the rows' traffic): the depthwise output written ONCE, pre-split
-                # (hl32), read by LDS-DMA, the gate folded into per-image project weights (csrc/pointwise_hl.hip)
-                y_hl, wg = hip_ops.depthwise_se_gate_weights(y, wd, bd, k, stride, s1, sb1, s2, sb2, wl_f32)
-                return hip_ops.pointwise_hl(y_hl, wg, bl, hip_ops.ACT_NONE, residual=res, out_fp32=True)
-            y, g = hip_ops.depthwise_se_gate(y, wd, bd, k, stride, s1, sb1, s2, sb2)
-            return hip_ops.pointwise_nhwc(y, wl, bl, hip_ops.ACT_NONE, gate=g, residual=res)
+            return mbconv_plan(x, self._folded(x), self.conv_dw.kernel_size[0], self.conv_dw.stride[0], None,
+                               x if self.has_residual else None)
         y = self.act1(self.bn1(self.conv_pw(x)))
         y = self.act2(self.bn2(self.conv_dw(y)))
         y = self.bn3(self.conv_pwl(self.se(y)))
         return y + x if self.has_residual else y
+
+
+def mbconv_plan(x, folded, k: int, stride: int, padding, residual):
+    """GPU inference plan of an inverted-residual block on its folded weights (InvertedResidual._fold's tuple): the B
+    family's InvertedResidual and EfficientNetV2's MBConv.  ``padding`` None = TF "SAME" (B family), else the depthwise
+    layer's (pad_t, pad_l) (V2).  Entry points are looked up on the hip_ops facade at call time.
+    NHWC, 4 launches: expand 1x1 (+BN+SiLU) -> depthwise (+BN+SiLU, + pooling partials) -> gate -> project 1x1 (+BN) with
+    the gate applied to its input rows and the skip connection added in the epilogue."""
+    we, be, wd, bd, wl, bl, s1, sb1, s2, sb2, wl_f32 = folded
+    B, cin, H, W = x.shape
+    cout, mid = wl_f32.shape
+    Ho, Wo = -(-H // stride), -(-W // stride)
+    if hip_ops.expand_depthwise_fusable(cin, we, k):
+        # 3 launches: the expanded tensor stays in LDS (csrc/mbconv_fused.hip)
+        y, g = hip_ops.expand_depthwise_se_gate(x, we, be, wd, bd, k, stride, s1, sb1, s2, sb2, padding=padding)
+        return hip_ops.pointwise_nhwc(y, wl, bl, hip_ops.ACT_NONE, gate=g, residual=residual)
+    y = hip_ops.pointwise_nhwc(x, we, be, hip_ops.ACT_SILU)
+    if isinstance(we, hip_ops.SplitWeight) and hip_ops.pointwise_hl_project_pays(B, Ho * Wo, mid, cout):
+        # stage 5's projects (long K, weights well under the rows' traffic): the depthwise output written ONCE, pre-split
+        # (hl32), read by LDS-DMA, the gate folded into per-image project weights (csrc/pointwise_hl.hip)
+        y_hl, wg = hip_ops.depthwise_se_gate_weights(y, wd, bd, k, stride, s1, sb1, s2, sb2, wl_f32, padding=padding)
+        return hip_ops.pointwise_hl(y_hl, wg, bl, hip_ops.ACT_NONE, residual=residual, out_fp32=True)
+    y, g = hip_ops.depthwise_se_gate(y, wd, bd, k, stride, s1, sb1, s2, sb2, padding=padding)
+    return hip_ops.pointwise_nhwc(y, wl, bl, hip_ops.ACT_NONE, gate=g, residual=residual)
 
 
 class GenEfficientNet(nn.Module):

@@ -22,11 +22,12 @@ stride-2 3x3 layer pads 1 on both sides here, 0 on top / 1 at the bottom there).
 identities in eval.
 
 Inference plan on the GPU (eval + no_grad): BN folded once per parameter version (_FoldedMixin); stem on csrc/stem.hip
-with padding (1, 1); a Fused-MBConv's 3x3 on the strided implicit GEMM (csrc/conv_strided.hip; SiLU and, for expand 1,
-the residual in its epilogue) and its 1x1 project on the pointwise kernel (residual in its epilogue); MBConv blocks on
-the B family's kernels (mbconv_fused / depthwise_se / pointwise_split) with explicit padding; the head on the pointwise
-kernel with SiLU.  Nothing of the encoder reaches MIOpen / hipBLASLt / ATen convolution; a shape no kernel takes raises
-HipLibraryError.  On the CPU or in training the plain module graph runs.
+with padding (1, 1); a Fused-MBConv's 3x3 on the implicit GEMM at stride 1 or 2 (csrc/conv_igemm.hip,
+ocv_conv3x3_nhwc_strided_fwd; SiLU and, for expand 1, the residual in its epilogue) and its 1x1 project on the pointwise
+kernel (residual in its epilogue); MBConv blocks on the B family's plan (efficientnet.mbconv_plan: mbconv_fused /
+depthwise_se / pointwise_split) with explicit padding; the head on the pointwise kernel with SiLU.  Nothing of the
+encoder reaches MIOpen / hipBLASLt / ATen convolution; a shape no kernel takes raises HipLibraryError.  On the CPU or in
+training the plain module graph runs.
 """
 from __future__ import annotations
 
@@ -34,7 +35,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip_ops
-from .efficientnet import _FoldedMixin, _dw_tap_major, fold_bn
+from .efficientnet import _FoldedMixin, _dw_tap_major, fold_bn, mbconv_plan
 
 BN_EPS = 1e-3
 
@@ -184,23 +185,9 @@ class MBConv(_FoldedMixin, nn.Module):
 
     def forward(self, x):
         if self._fast(x):
-            # the B family's InvertedResidual plan (efficientnet.py) with torchvision's symmetric padding
-            we, be, wd, bd, wl, bl, s1, sb1, s2, sb2, wl_f32 = self._folded(x)
+            # the B family's plan with torchvision's symmetric padding
             dw = self.block[1][0]
-            k, stride, pad = dw.kernel_size[0], dw.stride[0], dw.padding
-            B, cin, H, W = x.shape
-            mid, cout = dw.out_channels, self.out_channels
-            Ho, Wo = -(-H // stride), -(-W // stride)
-            res = x if self.use_res_connect else None
-            if hip_ops.expand_depthwise_fusable(cin, we, k):
-                y, g = hip_ops.expand_depthwise_se_gate(x, we, be, wd, bd, k, stride, s1, sb1, s2, sb2, padding=pad)
-                return hip_ops.pointwise_nhwc(y, wl, bl, hip_ops.ACT_NONE, gate=g, residual=res)
-            y = hip_ops.pointwise_nhwc(x, we, be, hip_ops.ACT_SILU)
-            if isinstance(we, hip_ops.SplitWeight) and hip_ops.pointwise_hl_project_pays(B, Ho * Wo, mid, cout):
-                y_hl, wg = hip_ops.depthwise_se_gate_weights(y, wd, bd, k, stride, s1, sb1, s2, sb2, wl_f32, padding=pad)
-                return hip_ops.pointwise_hl(y_hl, wg, bl, hip_ops.ACT_NONE, residual=res, out_fp32=True)
-            y, g = hip_ops.depthwise_se_gate(y, wd, bd, k, stride, s1, sb1, s2, sb2, padding=pad)
-            return hip_ops.pointwise_nhwc(y, wl, bl, hip_ops.ACT_NONE, gate=g, residual=res)
+            return mbconv_plan(x, self._folded(x), dw.kernel_size[0], dw.stride[0], dw.padding, x if self.use_res_connect else None)
         result = self.block(x)
         if self.use_res_connect:
             result = self.stochastic_depth(result)

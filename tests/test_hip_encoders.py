@@ -1,6 +1,7 @@
 """-m gpu: the EfficientNet-B1 / V2-S / V2-M encoders on the HIP path (reference modules/DenseFeatureExtractor.py:141-166).
 
-* the strided 3x3 implicit GEMM (ocv_conv3x3_nhwc_strided_fwd) against a float64 F.conv2d;
+* the strided 3x3 implicit GEMM (ocv_conv3x3_nhwc_strided_fwd) against a float64 F.conv2d, and at stride 1 bit for bit
+  against ocv_conv_nhwc_fwd;
 * each encoder's five skips and the whole extractor against the same module's float64 CPU forward on identical weights;
 * AdaBins / GraphBins end to end against the same module's CPU forward (depth: the project's 1e-3 max-rel bar);
 * graph replay of V2-M GraphBins bit for bit against eager dispatch;
@@ -68,6 +69,24 @@ def test_strided_conv3x3_vs_fp64(B, cin, cout, H, W, stride, pad, act, res):
                                 residual=None if r is None else r.cuda().contiguous(memory_format=cl), out_hw=(Ho, Wo))
     assert tuple(y.shape) == tuple(ref.shape)
     assert rel_dev(y, ref) < KERNEL_TOL
+
+
+@pytest.mark.parametrize("B,cin,cout,H,W", [(2, 24, 96, 32, 32), (1, 48, 40, 17, 23), (3, 80, 320, 31, 9)])
+def test_strided_conv3x3_at_stride1_equals_conv_nhwc(B, cin, cout, H, W):
+    """ocv_conv3x3_nhwc_strided_fwd at stride 1 with padding (1, 1) and ocv_conv_nhwc_fwd (k 3, one source) run the same
+    kernel: bias, SiLU and residual included, the outputs are equal bit for bit.  M = 2048 fills its pixel tiles exactly;
+    391 and 837 leave the last one ragged."""
+    g = torch.Generator().manual_seed(B * 100 + cin + cout + H + W)
+    cl = torch.channels_last
+    x = torch.randn(B, cin, H, W, generator=g).cuda().contiguous(memory_format=cl)
+    w = (torch.randn(cout, cin, 3, 3, generator=g) / np.sqrt(9 * cin)).cuda()
+    b = (torch.randn(cout, generator=g) * 0.1).cuda()
+    r = torch.randn(B, cout, H, W, generator=g).cuda().contiguous(memory_format=cl)
+    hi, lo = hip_ops.prep_conv_weight(w)
+    for res in (None, r):
+        y1 = hip_ops.conv_nhwc(x, None, hi, lo, b, 3, hip_ops.ACT_SILU, residual=res)
+        y2 = hip_ops.conv3x3_strided(x, hi, lo, b, 1, (1, 1), hip_ops.ACT_SILU, residual=res)
+        assert torch.equal(y1, y2)
 
 
 def _extractor(enc, seed):
