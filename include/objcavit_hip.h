@@ -461,8 +461,8 @@ int ocv_se_gate_fwd(const float* mean, const float* w1, const float* b1, const f
 int ocv_conv_nhwc_fwd(const float* x1, int C1, const float* x2, int C2, const void* w_hi, const void* w_lo,
                       const float* bias, const float* residual, float* y, int B, int H, int W, int Cout, int ksize,
                       int act, ocv_stream_t stream);
-/* The same convolution in EXACT fp32 (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fp32 fma chain, no split
- * operands), any odd k <= 7, any channel counts: the hand-written exact route for A/B numerics and for shapes the
+/* The same convolution in EXACT fp32 (v_mfma_f32_32x32x2_f32: fp32 fma chains over blocks of 32 input channels x all taps, summed in
+ * channel order; no split operands), any odd k <= 7, any channel counts: the hand-written exact route for A/B numerics and for shapes the
  * split-bf16 kernels do not take (5x slower by construction; not on any default path).  w_tap_major: fp32
  * [k*k][Cout][C1+C2].  Replaces the same reference lines as ocv_conv_nhwc_fwd. */
 int ocv_conv_nhwc_exact_fwd(const float* x1, int C1, const float* x2, int C2, const float* w_tap_major, const float* bias,
@@ -581,6 +581,9 @@ int ocv_conv3x3_winograd43_split_fwd(const void* x_hl, int Cin, const void* u_hi
  * the h x w grid whose one-pixel border ring holds one constant vector per column (zborder [9 Cout]: the tap products of
  * conv2's bias) and z stores only the (h-2) x (w-2) interior; zpad = 0: zborder NULL, z stores h x w. */
 int ocv_tap_interp_supported(int h, int w, int H, int W, int Cout);
+/* staging rounds per tap the launch for (h,w) -> (H,W) uses (1..6: which instantiation of the kernel runs; h, w include the
+ * border ring of zpad = 1); 0 for sizes below 1.  A host-side query for tests and tools. */
+int ocv_tap_interp_staging_rounds(int h, int w, int H, int W);
 int ocv_tap_interp_combine_fwd(const float* z, int h, int w, int zpad, const float* zborder, const float* s, const float* bias,
                                float* y, void* y_hl, int B, int H, int W, int Cout, int act, ocv_stream_t stream);
 /* the same with the element type of y_hl as a parameter (0 = bf16 pairs, 1 = fp16 pairs: ocv_conv_nhwc_split_x_fwd) */

@@ -1,6 +1,7 @@
 // Exact-fp32 convolution (k x k, k odd, stride 1, zero "same" padding) on NHWC activations for gfx950: the implicit GEMM
-// of csrc/conv_igemm.hip on v_mfma_f32_32x32x2_f32 -- bit-for-bit a k-ordered fp32 fma chain per output, no split
-// operands -- for callers that want the reference's own arithmetic class from a hand-written kernel: the A/B numerics
+// of csrc/conv_igemm.hip on v_mfma_f32_32x32x2_f32 -- per output a k-ordered fp32 fma chain over every block of 32 input
+// channels x all taps, the blocks' sums added in channel order (two levels: ONE chain over K = 20 016, the decoder's first
+// stage, sat at 6.6e-6 of max |y| against float64 where the float32 CPU convolution has 5e-7), no split operands -- for callers that want the reference's own arithmetic class from a hand-written kernel: the A/B numerics
 // route of the decoder / head convolutions (OCV_CONV=exact; round 1 used MIOpen for that) and the convolution shapes
 // the split-bf16 kernels do not take (channel counts that are not multiples of 4).  5x slower than the split-bf16
 // kernel by construction (64 instead of 3 x 4 matrix-pipe cycles per 32 x 32 x 2 block); not on any default path.
@@ -55,8 +56,9 @@ __global__ __launch_bounds__(256) void conv_exact_kernel(ExArgs p) {
     apix = am;
   }
 
-  f32x16 acc = {0};
+  f32x16 tot = {0};
   for (int c0 = 0; c0 < nchunk * XK; c0 += XK) {
+    f32x16 acc = {0};
     for (int t = 0; t < taps; ++t) {
       const int dy = t / p.ks - pad, dx = t % p.ks - pad;
       {
@@ -91,6 +93,8 @@ __global__ __launch_bounds__(256) void conv_exact_kernel(ExArgs p) {
       for (int s = 0; s < XK / 2; ++s) acc = mfma_32x32x2(arow[2 * s], wrow[2 * s], acc);
       __syncthreads();
     }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tot[r] += acc[r];
   }
   const int n = n0 + wave * 32 + l31;
   if (n >= p.Cout) return;
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void conv_exact_kernel(ExArgs p) {
   for (int r = 0; r < 16; ++r) {
     const long m = m0 + acc_row(r, hh);
     if (m < p.M) {
-      float v = ex_act(acc[r] + bv, p.act);
+      float v = ex_act(tot[r] + bv, p.act);
       if (p.res != nullptr) v += p.res[m * p.Cout + n];
       p.y[m * p.Cout + n] = v;
     }

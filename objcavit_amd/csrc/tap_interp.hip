@@ -296,6 +296,11 @@ extern "C" int ocv_tap_interp_supported(int h, int w, int H, int W, int Cout) {
   return ti_footprint(h, w, H, W) < FQ ? 1 : 0;                     // + the one spare slot the right-hand neighbour may touch
 }
 
+extern "C" int ocv_tap_interp_staging_rounds(int h, int w, int H, int W) {
+  if (h < 1 || w < 1 || H < 1 || W < 1) return 0;
+  return ocv_cdiv(ti_footprint(h, w, H, W) + 1, 32);                // (ti_launch's nj)
+}
+
 extern "C" int ocv_tap_interp_combine_fwd(const float* z, int h, int w, int zpad, const float* zborder, const float* s,
                                           const float* bias, float* y, void* y_hl, int B, int H, int W, int Cout, int act,
                                           ocv_stream_t stream) {
@@ -318,7 +323,7 @@ int ti_launch(const char* who, const float* z, int h, int w, int zpad, const flo
                 "%s: operands must be 16-byte aligned", who);
   OCV_CHECK_ARG(ocv_tap_interp_supported(h, w, H, W, Cout), "%s: the low-resolution footprint of an output tile "
                 "exceeds the staging buffer (h=%d w=%d H=%d W=%d): not an up-sampling by ~2 or more", who, h, w, H, W);
-  const int nj = ocv_cdiv(ti_footprint(h, w, H, W) + 1, 32);       // 1..6 staging rounds per tap (footprint + one spare slot)
+  const int nj = ocv_tap_interp_staging_rounds(h, w, H, W);        // 1..6 staging rounds per tap (footprint + one spare slot)
   TIArgs a{z, zborder, s, bias, y, (__bf16*)y_hl, h, w, H, W, Cout, (Cout + 31) / 32 * 32, act, zpad,
            H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f,
            ocv_cdiv(W, TX), ocv_cdiv(H, TY), nj * 32, hl_f16,

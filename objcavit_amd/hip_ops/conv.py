@@ -282,6 +282,11 @@ def tap_interp_supported(h: int, w: int, H: int, W: int, Cout: int) -> bool:
     return bool(_lib.load().ocv_tap_interp_supported(int(h), int(w), int(H), int(W), int(Cout)))
 
 
+def tap_interp_staging_rounds(h: int, w: int, H: int, W: int) -> int:
+    """Staging rounds per tap (1..6) of ``tap_interp_combine`` for an h x w source (border ring included) and an H x W result."""
+    return int(_lib.load().ocv_tap_interp_staging_rounds(int(h), int(w), int(H), int(W)))
+
+
 def tap_interp_combine(z: torch.Tensor, s: Optional[torch.Tensor], bias: Optional[torch.Tensor], size: Tuple[int, int],
                        act: int = ACT_NONE, out_fp32: bool = True, out_split: bool = False,
                        border: Optional[torch.Tensor] = None, split_f16: bool = False):

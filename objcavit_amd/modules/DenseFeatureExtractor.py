@@ -631,18 +631,22 @@ class Decoder(nn.Module):
                 b4.x = b4.x.contiguous(memory_format=cl)
             else:
                 b4 = b4.contiguous(memory_format=cl)
-        affine = self._up1_affine(b4, b3) if self._split3.usable(self.conv3.in_channels) and self.conv3.in_channels % 8 == 0 else None
+        stages = ((self.up1, b3), (self.up2, b2), (self.up3, b1), (self.up4, b0))
+        fin = self.final_upscale
+        # whether the all-split pipeline below runs is decided BEFORE up1's input may be left un-materialised: the per-stage route
+        # (e.g. 1280 features with do_final_upscale: 80 up-sampled channels are no whole 32-blocks) reads conv2's output itself
+        all_split = (self.up1.split_ready(_ShapeOnly(b4.shape[0], self.conv2.out_channels, b4.shape[2] + 2 * self.conv2.padding[0],
+                                                     b4.shape[3] + 2 * self.conv2.padding[1], device=b4.device), b3)
+                     and self._split3.usable(self.conv3.in_channels) and self.conv3.in_channels % 8 == 0
+                     and (fin is None or fin.split_ready(_ShapeOnly(b0.shape[0], self.up4._net[3].out_channels, b0.shape[2], b0.shape[3], device=b0.device), features[0])))
+        affine = self._up1_affine(b4, b3) if all_split else None
         if affine is not None:
             x = affine[0]
         else:
             if isinstance(b4, DeferredConv1x1):
                 b4 = b4.materialize()
             x = self._conv2_padded_1x1(b4)
-        stages = ((self.up1, b3), (self.up2, b2), (self.up3, b1), (self.up4, b0))
-        fin = self.final_upscale
-        if (all(up.split_ready(x, skip) for up, skip in stages[:1])
-                and self._split3.usable(self.conv3.in_channels) and self.conv3.in_channels % 8 == 0
-                and (fin is None or fin.split_ready(_ShapeOnly(b0.shape[0], self.up4._net[3].out_channels, b0.shape[2], b0.shape[3], device=b0.device), features[0]))):
+        if all_split:
             # all-split pipeline: the last stage hands conv3 its input pre-split; conv3 returns the fp32 feature map
             # (patch embedding reads it) AND its split copy, which rides along for the heads' 3x3 convolution.  Element type of
             # every split tensor: fp16 pairs (round 4) unless a weight of the pipeline does not fit them -- then bf16 pairs for

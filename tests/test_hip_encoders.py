@@ -189,6 +189,28 @@ def test_no_pytorch_convolution_on_the_gpu_path(monkeypatch, enc):
     assert out.shape == (1, 128, 240, 320) and bool(torch.isfinite(out).all())
 
 
+def test_no_pytorch_convolution_with_final_upscale_at_1280_features(monkeypatch):
+    """V2-S with do_final_upscale: 80 up-sampled channels are no whole 32-blocks, so the fifth stage cannot take the all-split
+    pipeline and the decoder runs stage by stage on conv2's materialised output (it once handed up1 the shape-only stand-in of
+    the composed route).  Still no PyTorch convolution: the 83-channel convolution runs on the exact-fp32 kernel; the output is
+    at full resolution and agrees with the module's float64 CPU forward."""
+    from objcavit_amd.modules.DenseFeatureExtractor import DenseFeatureExtractor
+    m = DenseFeatureExtractor(make_args(model="adabins", encoder_name="efficientnet-v2-s", do_final_upscale=True)).eval()
+    gen.load_into(m, 5)
+    img = gen.randn("img", (1, 3, 192, 208), 5)
+    ref = copy.deepcopy(m).double()(img.double())
+    m = m.cuda()
+
+    def boom(*a, **k):
+        raise AssertionError("PyTorch convolution on the GPU inference path")
+
+    monkeypatch.setattr(F, "conv2d", boom)
+    monkeypatch.setattr(torch.nn.Conv2d, "_conv_forward", boom)
+    out = m(img.cuda())
+    assert out.shape == ref.shape == (1, 128, 192, 208)
+    assert rel_dev(out, ref) < ENC_TOL
+
+
 G_FIXTURES = [("g9_effnet_b1_nyu_b1", "efficientnet-b1"), ("g9_effnet_b1_kitti_b2", "efficientnet-b1"),
               ("g10_effnet_v2s_nyu_b1", "efficientnet-v2-s"), ("g10_effnet_v2m_nyu_b1", "efficientnet-v2-m")]
 
