@@ -41,7 +41,8 @@ typedef void* ocv_stream_t;
 
 #define OCV_ABI_VERSION 5 /* 5: round 6 ADDED ocv_attention_set_dispatch (the library reads no environment variable any more),
  * ocv_conv3x3_packed_taps_k / ocv_conv3x3_split_packed_taps_fwd; nothing removed or changed: a caller built against 4 keeps working;
- * later ADDED (still 5: a new symbol changes nothing for an existing caller) ocv_conv3x3_nhwc_strided_fwd (EfficientNetV2);
+ * later ADDED (still 5: a new symbol changes nothing for an existing caller) ocv_conv3x3_nhwc_strided_fwd (EfficientNetV2),
+ * ocv_depth_metrics_loss_workspace_bytes / ocv_depth_metrics_loss_fwd (validation loss);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -616,6 +617,26 @@ int ocv_depth_metrics_fwd(const float* pred, const float* pred_mirror, int h, in
                           float min_depth, float max_depth, int crop_y0, int crop_y1, int crop_x0, int crop_x1,
                           long first_image_id, float* records, int B, void* workspace, size_t workspace_bytes,
                           ocv_stream_t stream);
+/* The same pass, also producing what the reference logs as val/loss (modules/GraphBinsLM.py:189-191,243; losses/LossWrapper.py:51-67,
+ * losses/SILogLoss.py:28-56, losses/BinsChamferLoss.py:21-37 with pytorch3d 0.7.0 chamfer_distance defaults).  records [B][10] are
+ * BIT-IDENTICAL to ocv_depth_metrics_fwd's.  loss_records [B][6] per image, over the mask min_depth < gt <= max_depth of the WHOLE
+ * map (no crop) and the resized prediction WITHOUT nan_to_num (a NaN under the mask gives NaN, as in the reference):
+ *   mean_g, mean_g2   means of g = log p - log gt and of g^2 (SILog = 10 sqrt(mean_g2 - 0.85 mean_g^2); a batch-wide call
+ *                     recombines sum n mean_g, sum n mean_g2, sum n)
+ *   n_mask            masked pixels = Chamfer targets T_b
+ *   cham_x            (1 / n_bins) sum_k min_t (c_k - t)^2, c_k = 0.5 (e_k + e_k+1) from bin_edges [B][n_bins + 1], t = masked gt
+ *   cham_y            (1 / max(T_b, 1)) sum_t min_k (t - c_k)^2           (both 0 for an image without targets)
+ *   first_image_id + b
+ * The edges may come in any order (the centres are sorted on the device).  A centre that is NaN (a NaN edge: a diverged bin head)
+ * is taken as +inf: the image's cham_x is then inf, its cham_y ignores that centre, nothing faults, other images are untouched and
+ * the result is still the same on every call.  1 <= n_bins <= 1024, min_depth >= 0.
+ * cham_y: minima in fp32 (bit-equal to the fp32 brute-force search); cham_x: in double from the unrounded centres (dense targets
+ * sit within ulps of a rounded centre); sums in double in a fixed order; no float atomics: two calls give bit-equal tables.  Workspace from ocv_depth_metrics_loss_workspace_bytes, 8-byte aligned. */
+size_t ocv_depth_metrics_loss_workspace_bytes(int B, int H, int W, int n_bins);
+int ocv_depth_metrics_loss_fwd(const float* pred, const float* pred_mirror, int h, int w, const float* gt, int H, int W,
+                               float min_depth, float max_depth, int crop_y0, int crop_y1, int crop_x0, int crop_x1,
+                               const float* bin_edges, int n_bins, long first_image_id, float* records, float* loss_records, int B,
+                               void* workspace, size_t workspace_bytes, ocv_stream_t stream);
 
 /* Tail of mViT / ObjCAViT.forward + glue of AdaBins / GraphBins.forward in one launch (modules/miniViT.py:33-42, modules/AdaBins.py:79-83):
  *   y = raw [B][n_bins] (the regressor's last Linear) -> OCV_BINNORM_LINEAR: relu(y) + 0.1 | OCV_BINNORM_SIGMOID: sigmoid(y) |

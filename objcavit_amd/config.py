@@ -60,6 +60,29 @@ _DATASETS = {
 }
 
 
+# the loss of all 57 reference configs (55 with these coefficients, 2 with [0.8, 0.1])
+_LOSS = dict(names=["silog", "bins_chamfer"], coeffs=[1, 0.1])
+
+
+def checked_loss(loss) -> AttrDict:
+    """``loss.names`` / ``loss.coeffs`` as losses/LossWrapper.py:29-34 asserts them.  'mse' is on the wrapper's list, but its
+    ``forward`` cannot take the wrapper's four positional arguments and no reference config names it: rejected."""
+    if not isinstance(loss, Mapping) or "names" not in loss or "coeffs" not in loss:
+        raise ValueError("the loss section needs 'names' and 'coeffs' (losses/LossWrapper.py:29-33)")
+    names, coeffs = list(loss["names"]), list(loss["coeffs"])
+    if len(names) < 1 or len(names) != len(coeffs):
+        raise ValueError("loss.names and loss.coeffs must have the same, non-zero length (losses/LossWrapper.py:31-34)")
+    for name in names:
+        if name == "mse":
+            raise ValueError("loss 'mse': the reference's MSELoss.forward cannot take LossWrapper's four positional arguments and no "
+                             "reference config uses it; supported: 'silog', 'bins_chamfer'")
+        if name not in ("silog", "bins_chamfer"):
+            raise ValueError(f"unrecognised loss function {name!r} (losses/LossWrapper.py:32)")
+    out = AttrDict(loss)
+    out["names"], out["coeffs"] = names, coeffs
+    return out
+
+
 def load_reference_config(path: str, basic_params: str = None) -> AttrDict:
     """A run's ``params/*.yaml`` as the reference sees it in validate / inference mode (main.py:161-179 ->
     misc_utils.check_and_validate_args, misc_utils.py:40-48): the file itself, with its ``nyu`` and ``kitti`` blocks
@@ -75,13 +98,16 @@ def load_reference_config(path: str, basic_params: str = None) -> AttrDict:
             blk = AttrDict(args.get(name) or {})
             blk.update(consts)
             args[name] = blk
+    # the loss the validation step evaluates (validation.val_loss); a file without the section has none, as in the reference
+    if args.get("loss") is not None:
+        args["loss"] = checked_loss(args["loss"])
     return args
 
 
 def make_args(model: str = "graphbins", dataset: str = "nyu", *, strategy: str = "learned",
               embedding_dim: int = 128, language: str = "control_obj_zeros_512", no_obj_sa: bool = False,
               use_2_saca: bool = False, n_bins: int = 256, encoder_name: str = "efficientnet-b5",
-              do_final_upscale: bool = False, **dataset_overrides: Any) -> AttrDict:
+              do_final_upscale: bool = False, loss_names: Any = None, loss_coeffs: Any = None, **dataset_overrides: Any) -> AttrDict:
     """The subset of the reference's YAML tree that the hot path reads."""
     ds = dict(_DATASETS[dataset])
     ds.update(dataset_overrides)
@@ -98,4 +124,6 @@ def make_args(model: str = "graphbins", dataset: str = "nyu", *, strategy: str =
     args["graphbins"] = dict(block, objcavit=objcavit, yolov7_chkpt="./yolov7_chkpts/yolov7-seg-lvis-e234.pt")
     args["adabins"] = dict(block)
     args[dataset] = ds
+    args["loss"] = checked_loss(dict(names=list(loss_names if loss_names is not None else _LOSS["names"]),
+                                     coeffs=list(loss_coeffs if loss_coeffs is not None else _LOSS["coeffs"])))
     return args

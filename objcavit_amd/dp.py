@@ -15,6 +15,9 @@ import torch
 import torch.distributed as dist
 
 RECORD_FIELDS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "log10", "delta1", "delta2", "delta3", "n_valid", "image_id")
+# columns 10 - 15 of the wide table of a ``loss=True`` validation step (objcavit_amd/validation.py: val_loss).  The functions below
+# key on RECORD_FIELDS' columns only (padding on column 9, averages over columns 0 - 7), so the wide table takes the same one gather.
+LOSS_FIELDS = ("mean_g", "mean_g2", "n_mask", "cham_x", "cham_y", "image_id")
 
 
 def init_from_env(device_type: str = "cuda") -> Tuple[int, int, int]:

@@ -243,6 +243,42 @@ def depth_metrics(pred: torch.Tensor, gt: torch.Tensor, min_depth: float, max_de
     return rec
 
 
+def depth_metrics_loss(pred: torch.Tensor, gt: torch.Tensor, bin_edges: torch.Tensor, min_depth: float, max_depth: float,
+                       crop: Optional[Tuple[int, int, int, int]] = None, pred_mirror: Optional[torch.Tensor] = None,
+                       first_image_id: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``depth_metrics`` and, on the same pass over the ground truth, the per-image pieces of the reference's validation loss
+    (losses/SILogLoss.py, losses/BinsChamferLoss.py): -> (records [B, 10], bit-identical to ``depth_metrics``; loss records [B, 6] =
+    dp.LOSS_FIELDS: mean_g, mean_g2, n_mask, cham_x, cham_y, image_id).  ``bin_edges`` [B, n_bins + 1] are those of the un-mirrored
+    forward; the loss mask has no crop and the prediction no nan_to_num.  ``validation.val_loss`` recombines the records."""
+    lib = _lib.load()
+    _req(pred, "pred"); _req(gt, "gt"); _req(bin_edges, "bin_edges")
+    if pred.dim() != 4 or gt.dim() != 4 or pred.shape[1] != 1 or gt.shape[1] != 1 or pred.shape[0] != gt.shape[0]:
+        raise ValueError("depth_metrics_loss: expected pred [B,1,h,w] and gt [B,1,H,W]")
+    if pred_mirror is not None:
+        _req(pred_mirror, "pred_mirror")
+        if pred_mirror.shape != pred.shape:
+            raise ValueError("depth_metrics_loss: pred_mirror must have pred's shape")
+    B, _, h, w = pred.shape
+    H, W = gt.shape[2:]
+    if bin_edges.dim() != 2 or bin_edges.shape[0] != B or not 2 <= bin_edges.shape[1] <= 1025:
+        raise ValueError(f"depth_metrics_loss: expected bin_edges [B = {B}, n_bins + 1] with 1 <= n_bins <= 1024, "
+                         f"got {tuple(bin_edges.shape)}")
+    if not 0.0 <= float(min_depth) < float(max_depth):
+        raise ValueError("depth_metrics_loss: need 0 <= min_depth < max_depth")
+    n_bins = int(bin_edges.shape[1]) - 1
+    y0, y1, x0, x1 = crop if crop is not None else (0, H, 0, W)
+    nb = lib.ocv_depth_metrics_loss_workspace_bytes(B, H, W, n_bins)
+    ws = workspace(nb, pred.device, "metrics")
+    rec = torch.empty(B, 10, dtype=torch.float32, device=pred.device)
+    lrec = torch.empty(B, 6, dtype=torch.float32, device=pred.device)
+    with timed("depth_metrics_loss"):
+        check(lib.ocv_depth_metrics_loss_fwd(pred.data_ptr(), _ptr(pred_mirror), h, w, gt.data_ptr(), H, W, float(min_depth),
+                                             float(max_depth), int(y0), int(y1), int(x0), int(x1), bin_edges.data_ptr(), n_bins,
+                                             int(first_image_id), rec.data_ptr(), lrec.data_ptr(), B, ws.data_ptr(), ws.numel(),
+                                             _stream()), "ocv_depth_metrics_loss_fwd")
+    return rec, lrec
+
+
 def stem_conv_same(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int,
                    act: int = ACT_NONE, padding: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """Dense 3x3 convolution with TF 'SAME' padding of an NCHW image, + bias + act; returns a channels_last tensor.

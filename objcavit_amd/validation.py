@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import hip_ops
-from .dp import RECORD_FIELDS
+from .dp import LOSS_FIELDS, RECORD_FIELDS
 
 
 def crop_box(args, H: int, W: int) -> Optional[Tuple[int, int, int, int]]:
@@ -37,8 +37,8 @@ class ValidationStep:
     AdaBins, a GraphedGraphBins captured for 2B images with ``object_group = B``); False: two forwards, as the reference issues
     them (A/B)."""
 
-    def __init__(self, model, args, flip_tta: bool = True, joint: bool = True):
-        self.model, self.args, self.flip_tta, self.joint = model, args, flip_tta, joint
+    def __init__(self, model, args, flip_tta: bool = True, joint: bool = True, loss: bool = False):
+        self.model, self.args, self.flip_tta, self.joint, self.loss = model, args, flip_tta, joint, loss
         ds = args[args.basic.dataset]
         self.min_depth, self.max_depth = float(ds.min_depth), float(ds.max_depth)
 
@@ -68,17 +68,29 @@ class ValidationStep:
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, depth_gt: torch.Tensor, first_image_id: int = 0):
-        """-> (records [B, 10] fp32 on the device, model output namedtuple of the un-mirrored forward)."""
+        """-> (records [B, 10] fp32 on the device, model output namedtuple of the un-mirrored forward).  With ``loss`` the
+        records are [B, 16]: RECORD_FIELDS + LOSS_FIELDS, the pieces of the reference's val/loss (``val_loss``), from the same
+        pass over the ground truth; the Chamfer term reads the bin edges of the un-mirrored forward, as the reference does."""
         if self.flip_tta:
             out, mirror = self._forward_pair(image)
         else:
             out, mirror = self._call(image), None
         H, W = depth_gt.shape[2:]
-        rec = hip_ops.depth_metrics(out.depth_pred.contiguous(), depth_gt.contiguous(), self.min_depth, self.max_depth,
-                                    crop=crop_box(self.args, H, W),
-                                    pred_mirror=None if mirror is None else mirror.contiguous(),
-                                    first_image_id=first_image_id)
-        return rec, out
+        return _records(out.depth_pred, mirror, getattr(out, "bin_edges", None), depth_gt, self.min_depth, self.max_depth,
+                        crop_box(self.args, H, W), first_image_id, self.loss), out
+
+
+def _records(pred, mirror, bin_edges, depth_gt, min_depth, max_depth, box, first_image_id, loss) -> torch.Tensor:
+    """The metric launch of a validation step: [B, 10], or [B, 16] with the loss pieces."""
+    mirror = None if mirror is None else mirror.contiguous()
+    if not loss:
+        return hip_ops.depth_metrics(pred.contiguous(), depth_gt.contiguous(), min_depth, max_depth, crop=box, pred_mirror=mirror,
+                                     first_image_id=first_image_id)
+    if bin_edges is None:
+        raise ValueError("a validation step with loss=True needs the model's bin_edges (the Chamfer term), and this output has none")
+    rec, lrec = hip_ops.depth_metrics_loss(pred.contiguous(), depth_gt.contiguous(), bin_edges.contiguous(), min_depth, max_depth,
+                                           crop=box, pred_mirror=mirror, first_image_id=first_image_id)
+    return torch.cat([rec, lrec], 1)
 
 
 def _takes_group(model) -> bool:
@@ -144,7 +156,7 @@ class PipelinedValidation:
     """
 
     def __init__(self, model, args, example_image: torch.Tensor, slots: int = 4, object_capacity: Optional[int] = None,
-                 flip_tta: bool = True):
+                 flip_tta: bool = True, loss: bool = False):
         from .graph import GraphedGraphBins
         if slots < 1:
             raise ValueError("PipelinedValidation: slots must be >= 1")
@@ -153,7 +165,7 @@ class PipelinedValidation:
             import warnings
             warnings.warn(f"PipelinedValidation: {note}", RuntimeWarning, stacklevel=2)
             hip_ops.ROUTE_REPORT["PipelinedValidation"] = note
-        self.args, self.flip_tta = args, flip_tta
+        self.args, self.flip_tta, self.loss = args, flip_tta, loss
         ds = args[args.basic.dataset]
         self.min_depth, self.max_depth = float(ds.min_depth), float(ds.max_depth)
         self.B = int(example_image.shape[0])
@@ -191,16 +203,17 @@ class PipelinedValidation:
     def _records(self, out, depth_gt: torch.Tensor, first_image_id: int) -> torch.Tensor:
         H, W = depth_gt.shape[2:]
         B = self.B
-        return hip_ops.depth_metrics(out.depth_pred[:B].contiguous(), depth_gt.contiguous(), self.min_depth, self.max_depth,
-                                     crop=crop_box(self.args, H, W),
-                                     pred_mirror=out.depth_pred[B:].contiguous() if self.flip_tta else None,
-                                     first_image_id=first_image_id)
+        # (with ``loss``: the graph's STATIC bin_edges, un-mirrored half, read by this launch on the slot's stream before the slot's
+        # next replay can overwrite them)
+        edges = getattr(out, "bin_edges", None)
+        return _records(out.depth_pred[:B], out.depth_pred[B:] if self.flip_tta else None, None if edges is None else edges[:B],
+                        depth_gt, self.min_depth, self.max_depth, crop_box(self.args, H, W), first_image_id, self.loss)
 
     def collect(self) -> torch.Tensor:
-        """Wait for every submitted step; -> records [N * B, 10] in submission order (and forget them).  The steps' inputs are held
+        """Wait for every submitted step; -> records [N * B, 10] ([N * B, 16] with ``loss``) in submission order (and forget them).  The steps' inputs are held
         until here (fp16 range guard: a tripped step is re-run on bf16 pairs): call it every few hundred steps on a long run."""
         if not self._pending:
-            return torch.empty(0, 10)
+            return torch.empty(0, len(RECORD_FIELDS) + (len(LOSS_FIELDS) if self.loss else 0))
         for p in self._pending:
             p[1].synchronize()
         recs = [p[0] for p in self._pending]
@@ -233,4 +246,35 @@ def totals(records: torch.Tensor) -> Dict[str, float]:
         else:
             out[k] = float((r[:, i] * n).sum() / tot)
     out["n_valid"] = int(n.sum())
+    return out
+
+
+def val_loss(records: torch.Tensor, args, group: int = 1) -> Dict[str, float]:
+    """The reference's ``val/loss`` from a wide record table [N, 16] (``ValidationStep(loss=True)``), in float64 on the host.
+    Consecutive groups of ``group`` images are recombined as ONE reference call each -- SILog (losses/SILogLoss.py:50-56) from the
+    group's sum n mean_g, sum n mean_g2, sum n (NaN for a group without a masked pixel, as there); Chamfer (pytorch3d defaults:
+    point reduction mean, batch reduction mean) sum (cham_x + cham_y) / group size -- and the groups averaged weighted by their
+    size.  ``group = 1`` is the reference's bs-1 epoch value (Lightning's mean of the per-step losses).
+    -> {"val/loss", "silog", "bins_chamfer"}: the total weighted by ``args.loss.coeffs`` and the two unweighted components."""
+    from .config import checked_loss
+    if records.dim() != 2 or records.shape[1] != len(RECORD_FIELDS) + len(LOSS_FIELDS):
+        raise ValueError(f"val_loss: expected the [N, 16] table of a loss=True validation step, got {tuple(records.shape)}")
+    if group < 1:
+        raise ValueError("val_loss: group must be >= 1")
+    if args.get("loss") is None:
+        raise ValueError("val_loss: args has no loss section (losses/LossWrapper.py:29)")
+    cfg = checked_loss(args["loss"])
+    r = records[records[:, RECORD_FIELDS.index("image_id")] >= 0].double().cpu()[:, len(RECORD_FIELDS):]
+    mg, mg2, n, cx, cy = (r[:, LOSS_FIELDS.index(k)] for k in ("mean_g", "mean_g2", "n_mask", "cham_x", "cham_y"))
+    comp = {"silog": 0.0, "bins_chamfer": 0.0}
+    N = int(r.shape[0])
+    for lo in range(0, N, group):
+        s = slice(lo, min(N, lo + group))
+        size = s.stop - s.start
+        nt = n[s].sum()
+        dg = (n[s] * mg2[s]).sum() / nt - (0.85 / nt ** 2) * (n[s] * mg[s]).sum() ** 2
+        comp["silog"] += size * float(10.0 * torch.sqrt(dg))
+        comp["bins_chamfer"] += size * float((cx[s] + cy[s]).sum() / size)
+    out = {k: (v / N if N else float("nan")) for k, v in comp.items()}
+    out["val/loss"] = sum(float(c) * out[k] for k, c in zip(cfg["names"], cfg["coeffs"]))
     return out
