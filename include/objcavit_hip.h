@@ -638,6 +638,35 @@ int ocv_depth_metrics_loss_fwd(const float* pred, const float* pred_mirror, int 
                                const float* bin_edges, int n_bins, long first_image_id, float* records, float* loss_records, int B,
                                void* workspace, size_t workspace_bytes, ocv_stream_t stream);
 
+/* Predict path, input end (modules/Preprocess.py:45-111, modules/GraphBinsLM.py:45,443): decoded frames -> model / metric inputs.
+ * ocv_frame_ingest_fwd: frames uint8 [B][Hs][Ws][3] (HWC; frame_stride / row_stride in BYTES, any alignment), the window of H x W pixels
+ *   at (top, left) -> out fp32 NCHW [B][3][H][W] with out[b][c][y][x] = table[c][frame value]; table fp32 [3][256] in device memory holds
+ *   the reference's ((v / image_norm_factor) - mean[c]) / std[c], evaluated by the host in fp32 in that order (the kernel divides nothing:
+ *   bit-equal to the reference arithmetic by construction).  mirror_too != 0: image b is also written flipped along W at
+ *   out + mirror_offset (elements; B * 3 * H * W puts the mirrored batch behind the batch: the [batch | mirrored batch] layout of the
+ *   validation step's joint forward).  W % 4 == 0 with a 16-byte aligned out: 16-byte stores; any other W: scalar stores.
+ * ocv_depth_ingest_fwd: ground truth uint16 [B][Hs][Ws] (strides in ELEMENTS) -> out fp32 [B][1][H][W] = float(v) / factor (1000 NYU,
+ *   256 KITTI), IEEE division: bit-equal to torch's fp32 division for all 65536 values.
+ * One launch each, no allocation, no synchronisation (hipGraph-capturable). */
+int ocv_frame_ingest_fwd(const uint8_t* frames, long frame_stride, long row_stride, int Hs, int Ws, int top, int left,
+                         const float* table, float* out, int B, int H, int W, int mirror_too, long mirror_offset,
+                         ocv_stream_t stream);
+int ocv_depth_ingest_fwd(const uint16_t* depth, long frame_stride, long row_stride, int Hs, int Ws, int top, int left, float factor,
+                         float* out, int B, int H, int W, ocv_stream_t stream);
+/* Predict path, output end (modules/GraphBinsLM.py:159-183,295-301,367, metrics/MetricsPreprocess.py:17-24): the map the metric pass
+ * above forms per pixel, written out.  pred [B][1][h][w], pred_mirror nullable and still mirrored (as for the metric pass):
+ *   d = resize_{H x W, bilinear, align_corners}(0.5 (clamp(pred) + clamp(flip(pred_mirror)))  or  clamp(pred)), nan -> min_depth,
+ *   +-inf -> max_depth; a NaN source pixel reaches every output pixel that has it as a tap, zero-weight taps included (ATen's 0 * NaN).
+ * Outputs, each nullable (at least one given):
+ *   depth      fp32 [B][1][H][W] = d
+ *   depth_u16  [B][H][W] = min(65535, max(0, rint(d * u16_scale))), ties to even (16-bit PNG convention: x 1000 NYU, x 256 KITTI)
+ *   rgb8       [B][H][W][3] = colormap[clamp(floor((d - vmin) * colormap_scale), 0, 255)], colormap uint8 [256][3] in device memory,
+ *              colormap_scale = 256 / (vmax - vmin) computed by the caller in fp32 (matplotlib's Normalize + colormap call).
+ * One launch; H * W % 8 == 0 with 16-byte aligned outputs: 16-byte stores; otherwise scalar stores.  Two calls give bit-equal output. */
+int ocv_depth_finalize_fwd(const float* pred, const float* pred_mirror, int h, int w, float min_depth, float max_depth, int H, int W,
+                           float* depth, uint16_t* depth_u16, float u16_scale, uint8_t* rgb8, const uint8_t* colormap, float vmin,
+                           float colormap_scale, int B, ocv_stream_t stream);
+
 /* Tail of mViT / ObjCAViT.forward + glue of AdaBins / GraphBins.forward in one launch (modules/miniViT.py:33-42, modules/AdaBins.py:79-83):
  *   y = raw [B][n_bins] (the regressor's last Linear) -> OCV_BINNORM_LINEAR: relu(y) + 0.1 | OCV_BINNORM_SIGMOID: sigmoid(y) |
  *   OCV_BINNORM_NONE: y (already normalised, e.g. a softmax);  widths_normed = y / sum_row(y) (NONE: y);

@@ -1,0 +1,164 @@
+"""hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip), full-resolution depth
+maps out (csrc/depth_finalize.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
+``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
+static input)."""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from .. import _lib
+from .._lib import check
+from ._core import _ptr, _req, _stream, timed
+
+
+def _frames_view(frames: torch.Tensor, name: str, dtype, channels: int) -> Tuple[int, int, int, int, int]:
+    """(B, Hs, Ws, frame stride, row stride in elements) of a decoded-frame tensor [B, Hs, Ws(, 3)] whose pixels are dense within a row;
+    rows and frames may be strided (a view into a larger buffer)."""
+    _req(frames, name, dtype, contiguous=False)
+    want = 4 if channels == 3 else 3
+    if frames.dim() != want or (channels == 3 and frames.shape[3] != 3):
+        raise ValueError(f"{name}: expected {'[B, Hs, Ws, 3] (HWC)' if channels == 3 else '[B, Hs, Ws]'}, got {tuple(frames.shape)}")
+    B, Hs, Ws = (int(s) for s in frames.shape[:3])
+    if B < 1 or Hs < 1 or Ws < 1:
+        raise ValueError(f"{name}: empty frames {tuple(frames.shape)}")
+    st = frames.stride()
+    if (channels == 3 and (st[3] != 1 or st[2] != 3)) or (channels == 1 and st[2] != 1):
+        raise ValueError(f"{name}: the pixels of a row must be dense (strides {st})")
+    row = int(st[1]) if Hs > 1 else Ws * channels
+    frame = int(st[0]) if B > 1 else Hs * row
+    if row < Ws * channels or frame < (Hs - 1) * row + Ws * channels:
+        raise ValueError(f"{name}: overlapping rows / frames (strides {st})")
+    return B, Hs, Ws, frame, row
+
+
+def _window(Hs: int, Ws: int, top: int, left: int, size: Optional[Tuple[int, int]], name: str) -> Tuple[int, int]:
+    H, W = (Hs - top, Ws - left) if size is None else (int(size[0]), int(size[1]))
+    if top < 0 or left < 0 or H < 1 or W < 1 or top + H > Hs or left + W > Ws:
+        raise ValueError(f"{name}: crop window {H} x {W} at ({top}, {left}) does not fit a {Hs} x {Ws} frame")
+    return H, W
+
+
+def _out_slice(out: Optional[torch.Tensor], shape: Tuple[int, ...], dtype, device, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req(out, f"{name}: out", dtype)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{name}: out must be {tuple(shape)}, got {tuple(out.shape)}")
+    return out
+
+
+def frame_ingest(frames_u8: torch.Tensor, table: torch.Tensor, top: int = 0, left: int = 0, size: Optional[Tuple[int, int]] = None,
+                 mirror_too: bool = False, out: Optional[torch.Tensor] = None, out_index: int = 0) -> torch.Tensor:
+    """uint8 frames [B, Hs, Ws, 3] (rows / frames may be strided) -> fp32 NCHW: the ``size`` = (H, W) window at (top, left), every
+    channel value looked up in ``table`` (fp32 [3, 256] on the device: ``predict.normalisation_table``).  ``mirror_too``: the result
+    has a second half, the first flipped along W -- the [batch | mirrored batch] input of the validation step's joint forward.
+    ``out``: write into this tensor ([N, 3, H, W], N >= B, or N = 2 * (images) with ``mirror_too``) at images ``out_index`` ..
+    ``out_index + B`` (and N / 2 + the same for the mirrors): a captured graph's static input, or one batch tensor filled by one launch
+    per differently sized frame.  -> the tensor written."""
+    lib = _lib.load()
+    B, Hs, Ws, frame, row = _frames_view(frames_u8, "frames_u8", torch.uint8, 3)
+    _req(table, "table")
+    if tuple(table.shape) != (3, 256):
+        raise ValueError(f"frame_ingest: table must be [3, 256], got {tuple(table.shape)}")
+    H, W = _window(Hs, Ws, int(top), int(left), size, "frame_ingest")
+    if out is None:
+        out = torch.empty((2 * B if mirror_too else B, 3, H, W), dtype=torch.float32, device=frames_u8.device)
+        out_index = 0
+    else:
+        _req(out, "frame_ingest: out")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (3, H, W):
+            raise ValueError(f"frame_ingest: out must be [N, 3, {H}, {W}], got {tuple(out.shape)}")
+    N = int(out.shape[0])
+    half = N // 2 if mirror_too else N
+    if (mirror_too and N % 2) or out_index < 0 or out_index + B > half:
+        raise ValueError(f"frame_ingest: {B} image(s) at index {out_index} do not fit out {tuple(out.shape)}"
+                         f"{' (first half: the second takes the mirrors)' if mirror_too else ''}")
+    plane = 3 * H * W
+    with timed("frame_ingest"):
+        check(lib.ocv_frame_ingest_fwd(frames_u8.data_ptr(), frame, row, Hs, Ws, int(top), int(left), table.data_ptr(),
+                                       out.data_ptr() + 4 * plane * int(out_index), B, H, W, 1 if mirror_too else 0, half * plane,
+                                       _stream()), "ocv_frame_ingest_fwd")
+    return out
+
+
+def depth_ingest(depth_u16: torch.Tensor, factor: float, top: int = 0, left: int = 0, size: Optional[Tuple[int, int]] = None,
+                 out: Optional[torch.Tensor] = None, out_index: int = 0) -> torch.Tensor:
+    """uint16 ground-truth depth [B, Hs, Ws] (as in the 16-bit PNGs) -> fp32 metres [B, 1, H, W] = float(v) / ``factor`` over the same
+    window arguments as ``frame_ingest`` (modules/Preprocess.py:45-65; 1000 for NYU, 256 for KITTI)."""
+    lib = _lib.load()
+    B, Hs, Ws, frame, row = _frames_view(depth_u16, "depth_u16", torch.uint16, 1)
+    H, W = _window(Hs, Ws, int(top), int(left), size, "depth_ingest")
+    if not float(factor) > 0.0:
+        raise ValueError("depth_ingest: factor must be positive")
+    if out is None:
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=depth_u16.device)
+        out_index = 0
+    else:
+        _req(out, "depth_ingest: out")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (1, H, W) or out_index < 0 or out_index + B > out.shape[0]:
+            raise ValueError(f"depth_ingest: out must be [N >= {out_index + B}, 1, {H}, {W}], got {tuple(out.shape)}")
+    with timed("depth_ingest"):
+        check(lib.ocv_depth_ingest_fwd(depth_u16.data_ptr(), frame, row, Hs, Ws, int(top), int(left), float(factor),
+                                       out.data_ptr() + 4 * H * W * int(out_index), B, H, W, _stream()), "ocv_depth_ingest_fwd")
+    return out
+
+
+def colormap_scale(vmin: float, vmax: float) -> float:
+    """256 / (vmax - vmin) in fp32, as ``depth_finalize`` hands it to the kernel."""
+    lo, hi = torch.tensor(float(vmin), dtype=torch.float32), torch.tensor(float(vmax), dtype=torch.float32)
+    if not bool(hi > lo):
+        raise ValueError("colour range: vmax must be above vmin")
+    return float(torch.tensor(256.0, dtype=torch.float32) / (hi - lo))
+
+
+def depth_finalize(pred: torch.Tensor, min_depth: float, max_depth: float, size: Tuple[int, int],
+                   pred_mirror: Optional[torch.Tensor] = None, want: Tuple[str, ...] = ("depth",), u16_scale: float = 1000.0,
+                   colormap: Optional[torch.Tensor] = None, vmin: Optional[float] = None, vmax: Optional[float] = None,
+                   out: Optional[dict] = None) -> dict:
+    """The model's depth_pred [B, 1, h, w] (+ ``pred_mirror``, the output for the mirrored image, still mirrored) -> the final map at
+    ``size`` = (H, W): flip-TTA average of the clamped maps (or the clamped map), bilinear align_corners resize, nan -> min_depth,
+    +-inf -> max_depth -- the map ``depth_metrics`` evaluates, materialised.  ``want``: any of "depth" (fp32 [B, 1, H, W]),
+    "depth_u16" ([B, H, W] = min(65535, rint(depth * u16_scale))), "rgb8" ([B, H, W, 3] through ``colormap``, uint8 [256, 3] on the
+    device, over [vmin, vmax]; default the depth range).  ``out``: {name: tensor} to write into.  -> {name: tensor}."""
+    lib = _lib.load()
+    _req(pred, "pred")
+    if pred.dim() != 4 or pred.shape[1] != 1:
+        raise ValueError("depth_finalize: expected pred [B, 1, h, w]")
+    if pred_mirror is not None:
+        _req(pred_mirror, "pred_mirror")
+        if pred_mirror.shape != pred.shape:
+            raise ValueError("depth_finalize: pred_mirror must have pred's shape")
+    want = tuple(want)
+    bad = set(want) - {"depth", "depth_u16", "rgb8"}
+    if bad or not want:
+        raise ValueError(f"depth_finalize: want must name some of 'depth', 'depth_u16', 'rgb8' (got {want})")
+    B, _, h, w = (int(s) for s in pred.shape)
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError("depth_finalize: bad output size")
+    out = dict(out or {})
+    res = {}
+    if "depth" in want:
+        res["depth"] = _out_slice(out.get("depth"), (B, 1, H, W), torch.float32, pred.device, "depth_finalize")
+    if "depth_u16" in want:
+        res["depth_u16"] = _out_slice(out.get("depth_u16"), (B, H, W), torch.uint16, pred.device, "depth_finalize")
+    scale = 0.0
+    lo = float(min_depth) if vmin is None else float(vmin)
+    if "rgb8" in want:
+        if colormap is None:
+            raise ValueError("depth_finalize: 'rgb8' needs a colormap (uint8 [256, 3] on the device: predict.colormap_table)")
+        _req(colormap, "colormap", torch.uint8)
+        if tuple(colormap.shape) != (256, 3):
+            raise ValueError(f"depth_finalize: colormap must be [256, 3], got {tuple(colormap.shape)}")
+        scale = colormap_scale(lo, float(max_depth) if vmax is None else float(vmax))
+        res["rgb8"] = _out_slice(out.get("rgb8"), (B, H, W, 3), torch.uint8, pred.device, "depth_finalize")
+    with timed("depth_finalize"):
+        check(lib.ocv_depth_finalize_fwd(pred.data_ptr(), _ptr(pred_mirror), h, w, float(min_depth), float(max_depth), H, W,
+                                         _ptr(res.get("depth")), _ptr(res.get("depth_u16")), float(u16_scale), _ptr(res.get("rgb8")),
+                                         _ptr(colormap) if "rgb8" in want else None, lo, scale, B, _stream()), "ocv_depth_finalize_fwd")
+    return res
+
+
+__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale"]

@@ -1,0 +1,349 @@
+"""Frames in, depth out: the reference's predict mode around the model (row N5 of DESIGN.md section 6b), on the device.
+
+``Predictor(model, args)(frames_u8)`` takes DECODED frames -- uint8 HWC, as an image decoder returns them -- and does what the
+reference does between a file and its saved results (modules/GraphBinsLM.py:285-421): / image_norm_factor, KITTI benchmark crop,
+ImageNet normalisation (modules/Preprocess.py:68-111, GraphBinsLM.py:45,443) in ONE launch that also writes the mirrored batch
+(csrc/frame_ingest.hip); the same joint 2B-image forward as ``ValidationStep``; then the final map -- clamp, un-mirror, average,
+bilinear align_corners resize to the input size, nan / inf fix (GraphBinsLM.py:159-183, metrics/MetricsPreprocess.py:17-24) -- written
+out in one more launch as fp32 metres, as the datasets' 16-bit PNG values and as a colour-mapped picture (csrc/depth_finalize.hip).
+With ground truth the existing metric launch adds the per-image records of a validation step.  ``flip_tta=False`` is the
+reference's own predict step, which uses no test-time augmentation (GraphBinsLM.py:295-301).  ``PipelinedPredictor`` keeps several
+such steps in flight on captured graphs, as ``PipelinedValidation`` does.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import List, Optional, Sequence, Tuple, Union
+
+import torch
+
+from . import hip_ops
+from ._lib import HipLibraryError
+from .dp import LOSS_FIELDS, RECORD_FIELDS
+from .validation import _joint_fits, _records, _takes_group, crop_box, hw_queue_note
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
+IMAGENET_STD = (0.229, 0.224, 0.225)
+KB_CROP = (352, 1216)                          # modules/Preprocess.py:104-107
+_DEPTH_FACTOR = {"nyu": 1000.0, "kitti": 256.0}     # params/basicParams.yaml depth_norm_factor of the two dataset blocks
+WANT = ("depth", "depth_u16", "rgb8")
+
+PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "records", "bin_edges"])
+
+Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
+
+
+def _dataset(args):
+    return args[args.basic.dataset]
+
+
+def normalisation_table(args) -> torch.Tensor:
+    """fp32 [3, 256] on the host: table[c][v] = ((v / image_norm_factor) - mean[c]) / std[c], the reference's own fp32 statements in
+    their order (modules/Preprocess.py:85-87: float32 array /= factor; torchvision Normalize: sub mean, div std, both fp32 tensors)
+    evaluated for every value a uint8 channel can take."""
+    factor = float(_dataset(args).get("image_norm_factor", 255.0))
+    v = torch.arange(256, dtype=torch.float32)
+    mean = torch.tensor(IMAGENET_MEAN, dtype=torch.float32).view(3, 1)
+    std = torch.tensor(IMAGENET_STD, dtype=torch.float32).view(3, 1)
+    return ((v / factor).view(1, 256) - mean) / std
+
+
+def depth_factor(args) -> float:
+    """uint16 ground-truth units per metre (modules/Preprocess.py:59-64): the dataset block's ``depth_norm_factor``, else the
+    reference's constants (1000 NYU, 256 KITTI)."""
+    return float(_dataset(args).get("depth_norm_factor", _DEPTH_FACTOR[args.basic.dataset]))
+
+
+def kb_crop_origin(Hs: int, Ws: int) -> Tuple[int, int]:
+    """(top, left) of the 352 x 1216 KITTI benchmark crop of an Hs x Ws frame (modules/Preprocess.py:104-105)."""
+    if Hs < KB_CROP[0] or Ws < KB_CROP[1]:
+        raise ValueError(f"the KITTI benchmark crop needs frames of at least {KB_CROP[0]} x {KB_CROP[1]}, got {Hs} x {Ws}")
+    return int(Hs - KB_CROP[0]), int((Ws - KB_CROP[1]) / 2)
+
+
+def colormap_table(name: str = "inferno_r") -> torch.Tensor:
+    """uint8 [256, 3] on the host: the 256 RGB rows of a matplotlib colormap (imported here, lazily: nothing else needs matplotlib).
+    A reversed map (``inferno_r``) is its base table read backwards."""
+    import matplotlib
+    import numpy as np
+    lut = matplotlib.colormaps[name](np.arange(256), bytes=True)[:, :3]
+    return torch.from_numpy(np.ascontiguousarray(lut)).to(torch.uint8)
+
+
+def _window(args, Hs: int, Ws: int, crop) -> Tuple[int, int, int, int]:
+    """(top, left, H, W): ``crop`` as given, else the dataset's rule -- the KITTI benchmark crop with ``do_kb_crop``, else the frame."""
+    if crop is not None:
+        top, left, H, W = (int(c) for c in crop)
+        return top, left, H, W
+    if _dataset(args).get("do_kb_crop", False):
+        return kb_crop_origin(Hs, Ws) + KB_CROP
+    return 0, 0, Hs, Ws
+
+
+def _frame_list(frames: Frames, what: str, dims: int) -> List[torch.Tensor]:
+    """A batch tensor, or a list of single frames of varying size, as a list of [b, ...] batch tensors."""
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() != dims:
+            raise ValueError(f"{what}: expected a [B, Hs, Ws{', 3' if dims == 4 else ''}] tensor or a list of single frames, got {tuple(frames.shape)}")
+        return [frames]
+    out = []
+    for f in frames:
+        if not isinstance(f, torch.Tensor) or f.dim() != dims - 1:
+            raise ValueError(f"{what}: a list holds single frames [Hs, Ws{', 3' if dims == 4 else ''}]")
+        out.append(f.unsqueeze(0))
+    if not out:
+        raise ValueError(f"{what}: empty list")
+    return out
+
+
+class _Ends:
+    """What both predictors share: the device tables and the two ends around a forward."""
+
+    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop):
+        self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
+        ds = _dataset(args)
+        self.min_depth, self.max_depth = float(ds.min_depth), float(ds.max_depth)
+        self.vmin = self.min_depth if vmin is None else float(vmin)
+        self.vmax = self.max_depth if vmax is None else float(vmax)
+        self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
+        self._table_host = normalisation_table(args)
+        self._colormap_host = colormap
+        self._dev = {}
+
+    def _on(self, device: torch.device, want_cmap: bool):
+        key = (device.type, device.index)
+        ent = self._dev.get(key)
+        if ent is None:
+            ent = self._dev[key] = {"table": self._table_host.to(device)}
+        if want_cmap and "cmap" not in ent:
+            cm = self._colormap_host
+            if cm is None or isinstance(cm, str):
+                cm = colormap_table(cm or "inferno_r")
+            ent["cmap"] = cm.to(device=device, dtype=torch.uint8).contiguous()
+        return ent
+
+    def window_of(self, frames: List[torch.Tensor]) -> Tuple[int, int]:
+        sizes = {_window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)[2:] for f in frames}
+        if len(sizes) != 1:
+            raise ValueError(f"frames of one batch must crop to one size, got {sorted(sizes)}")
+        return sizes.pop()
+
+    def ingest(self, frames: List[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``."""
+        for f in frames:
+            if f.device.type != "cuda":
+                raise HipLibraryError(f"frames are on {f.device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
+        H, W = self.window_of(frames)
+        B = sum(int(f.shape[0]) for f in frames)
+        table = self._on(frames[0].device, False)["table"]
+        if out is None:
+            out = torch.empty((2 * B if self.flip_tta else B, 3, H, W), dtype=torch.float32, device=frames[0].device)
+        elif int(out.shape[0]) != (2 * B if self.flip_tta else B):
+            raise ValueError(f"{B} frame(s) do not fill a batch of {tuple(out.shape)}")
+        i = 0
+        for f in frames:
+            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
+            hip_ops.frame_ingest(f, table, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
+            i += int(f.shape[0])
+        return out
+
+    def ground_truth(self, depth_gt, B: int) -> Optional[torch.Tensor]:
+        """fp32 [B, 1, H, W] as given, or uint16 frames (tensor or list) through ``depth_ingest`` with the frames' crop rule."""
+        if depth_gt is None:
+            return None
+        if isinstance(depth_gt, torch.Tensor) and depth_gt.dtype == torch.float32:
+            if depth_gt.dim() != 4 or depth_gt.shape[0] != B or depth_gt.shape[1] != 1:
+                raise ValueError(f"depth_gt: expected fp32 [{B}, 1, H, W] or uint16 frames, got {tuple(depth_gt.shape)}")
+            return depth_gt.contiguous()
+        maps = _frame_list(depth_gt, "depth_gt", 3)
+        H, W = self.window_of(maps)
+        if sum(int(m.shape[0]) for m in maps) != B:
+            raise ValueError("depth_gt: one ground-truth map per frame")
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=maps[0].device)
+        i = 0
+        for m in maps:
+            top, left, _, _ = _window(self.args, int(m.shape[1]), int(m.shape[2]), self.crop)
+            hip_ops.depth_ingest(m, depth_factor(self.args), top, left, (H, W), out=out, out_index=i)
+            i += int(m.shape[0])
+        return out
+
+    def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int, want: Tuple[str, ...],
+               edges) -> PredictResult:
+        """Final map + (with ground truth) the metric launch, on the current stream."""
+        pred = out.contiguous()
+        mirror = None if mirror is None else mirror.contiguous()
+        maps = {}
+        if want:
+            cmap = self._on(pred.device, True)["cmap"] if "rgb8" in want else None
+            maps = hip_ops.depth_finalize(pred, self.min_depth, self.max_depth, size, pred_mirror=mirror, want=want,
+                                          u16_scale=self.u16_scale, colormap=cmap, vmin=self.vmin, vmax=self.vmax)
+        rec = None
+        if depth_gt is not None:
+            H, W = depth_gt.shape[2:]
+            rec = _records(pred, mirror, edges, depth_gt, self.min_depth, self.max_depth, crop_box(self.args, H, W), first_image_id,
+                           self.loss)
+        return PredictResult(maps.get("depth"), maps.get("depth_u16"), maps.get("rgb8"), rec, edges)
+
+
+def _check_want(want) -> Tuple[str, ...]:
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = set(want) - set(WANT)
+    if bad:
+        raise ValueError(f"want: unknown output(s) {sorted(bad)}; expected some of {WANT}")
+    return want
+
+
+class Predictor:
+    """``Predictor(model, args)(frames_u8, depth_gt=None, first_image_id=0, want=("depth",))`` -> ``PredictResult``.
+
+    ``frames_u8``: a uint8 device tensor [B, Hs, Ws, 3] or a list of [Hs_i, Ws_i, 3] tensors (KITTI's frames vary in size; every
+    frame is cropped to 352 x 1216 by its own origin, one ingest launch per frame into one batch tensor).  ``depth_gt``: fp32
+    [B, 1, H, W] metres, or the uint16 maps of the 16-bit PNGs (tensor or list; same crop, / depth_norm_factor).  ``want``: any of
+    "depth" (fp32 [B, 1, H, W] at the cropped input size), "depth_u16" ([B, H, W], x ``u16_scale``: the dataset's PNG convention),
+    "rgb8" ([B, H, W, 3] through ``colormap`` -- a uint8 [256, 3] tensor or a matplotlib name, default "inferno_r" -- over
+    [vmin, vmax], default the dataset's depth range).  ``records``: the [B, 10] / [B, 16] table of ``ValidationStep`` when ground
+    truth is given; ``bin_edges``: those of the un-mirrored forward (a captured graph hands out its static tensor).
+    ``model``: GraphBins / AdaBins, or a ``GraphedGraphBins`` captured for the [batch | mirrored batch] shape with
+    ``object_group = B`` -- the frames are then ingested straight into its static input and it is called through ``checked``."""
+
+    def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
+                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None):
+        self.model = model
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop)
+        self.flip_tta = flip_tta
+
+    def _call(self, *a):
+        fn = getattr(self.model, "checked", None)
+        return fn(*a) if fn is not None else self.model(*a)
+
+    def _forward(self, frames: List[torch.Tensor], B: int):
+        """(output of the un-mirrored forward, mirrored forward's depth or None): ``ValidationStep._forward_pair`` fed by the ingest."""
+        static = getattr(self.model, "static_image", None)
+        if not self.flip_tta:
+            fits = static is not None and int(static.shape[0]) == B and tuple(static.shape[2:]) == self.ends.window_of(frames)
+            return self._call(self.ends.ingest(frames, out=static if fits else None)), None
+        joint = getattr(self.model, "images_are_independent", False) and _joint_fits(self.model, B)
+        fits = joint and static is not None and tuple(static.shape[2:]) == self.ends.window_of(frames)
+        both = self.ends.ingest(frames, out=static if fits else None)
+        if not joint:
+            first = self._call(both[:B])
+            if static is not None:
+                first = type(first)(**{k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in first._asdict().items()})
+            return first, self._call(both[B:]).depth_pred
+        out = self.model(both, None, None, None, B) if _takes_group(self.model) else self._call(both)
+        first = type(out)(**{k: (None if v is None else v[:B]) for k, v in out._asdict().items()})
+        return first, out.depth_pred[B:]
+
+    @torch.no_grad()
+    def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",)) -> PredictResult:
+        want = _check_want(want)
+        frames = _frame_list(frames_u8, "frames_u8", 4)
+        B = sum(int(f.shape[0]) for f in frames)
+        size = self.ends.window_of(frames)
+        out, mirror = self._forward(frames, B)
+        gt = self.ends.ground_truth(depth_gt, B)
+        return self.ends.finish(out.depth_pred, mirror, size, gt, first_image_id, want, getattr(out, "bin_edges", None))
+
+
+class PipelinedPredictor:
+    """``slots`` predict steps IN FLIGHT, modelled on ``PipelinedValidation``: one captured graph of the joint [batch | mirrored batch]
+    forward per slot, each on a stream with a hardware queue of its own (``hip_ops.independent_streams``).  ``submit`` ingests the
+    frames DIRECTLY into the slot's static input -- no ``flip``, no ``cat``, no ``copy_`` of the image: the graph sees its own
+    pointer and skips its copy --, replays, and writes the final map (and, with ground truth, the metric records) on the slot's
+    stream; ``collect`` returns the ``PredictResult`` of every submitted step in submission order, reads the steps' fp16 range-guard
+    words in one host copy and re-runs a tripped step from its kept frames on the bf16-pair capture.  ``bin_edges`` of a result is
+    None unless ``want`` names "bin_edges" (the graph's static tensor is then copied per step).  Wants ``GPU_MAX_HW_QUEUES`` >= slots
+    set before the HIP runtime starts, like ``PipelinedValidation``.
+
+        pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
+        for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
+            pp.submit(frame, first_image_id=i)
+        results = pp.collect()
+    """
+
+    def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
+                 flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
+                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
+                 crop: Optional[Tuple[int, int, int, int]] = None):
+        from .graph import GraphedGraphBins
+        if slots < 1:
+            raise ValueError("PipelinedPredictor: slots must be >= 1")
+        note = hw_queue_note(slots)
+        if note:
+            import warnings
+            warnings.warn(f"PipelinedPredictor: {note}", RuntimeWarning, stacklevel=2)
+            hip_ops.ROUTE_REPORT["PipelinedPredictor"] = note
+        self.want_edges = "bin_edges" in tuple(want)
+        self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop)
+        self.flip_tta = flip_tta
+        ex = _frame_list(example_frames, "example_frames", 4)
+        self.B = sum(int(f.shape[0]) for f in ex)
+        self.size = self.ends.window_of(ex)
+        both = self.ends.ingest(ex)
+        if "rgb8" in self.want:
+            self.ends._on(both.device, True)                 # the colour table is uploaded here, not inside a step
+        streams = hip_ops.independent_streams(slots, both.device) if slots > 1 else [None]
+        self.graphs = [GraphedGraphBins(model, both, object_capacity=object_capacity, object_group=self.B if flip_tta else None,
+                                        in_flight=slots, stream=streams[k]) for k in range(slots)]
+        self._next = 0
+        self._pending = []
+        self.rerun_steps = 0                                 # steps re-run on bf16 pairs by collect() (fp16 range guard)
+
+    def _finish(self, out, gt, first_image_id: int) -> PredictResult:
+        B = self.B
+        edges = getattr(out, "bin_edges", None)
+        edges = None if edges is None else edges[:B]
+        res = self.ends.finish(out.depth_pred[:B], out.depth_pred[B:] if self.flip_tta else None, self.size, gt, first_image_id,
+                               self.want, edges)
+        return res._replace(bin_edges=edges.clone() if (self.want_edges and edges is not None) else None)
+
+    @torch.no_grad()
+    def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None) -> None:
+        """Enqueue one predict step on the next slot's stream; returns at once."""
+        frames = _frame_list(frames_u8, "frames_u8", 4)
+        if sum(int(f.shape[0]) for f in frames) != self.B or self.ends.window_of(frames) != self.size:
+            raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")
+        g = self.graphs[self._next]
+        self._next = (self._next + 1) % len(self.graphs)
+        caller = torch.cuda.current_stream(frames[0].device)
+        g.stream.wait_stream(caller)                         # the frames / ground truth were produced on the caller's stream
+        with torch.cuda.stream(g.stream):
+            self.ends.ingest(frames, out=g.static_image)
+            out = g(g.static_image, object_features, object_xywh_list) if g.objects is not None else g(g.static_image)
+            gt = self.ends.ground_truth(depth_gt, self.B)
+            res = self._finish(out, gt, first_image_id)
+        held = list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
+        for t in held:
+            t.record_stream(g.stream)                        # the caching allocator must not recycle them under the slot's launches
+        # frames and ground truth stay referenced until collect(): a step whose range guard tripped is re-run from them
+        self._pending.append((res, g.stream, g.last_flag, g, (frames, depth_gt, first_image_id, object_features, object_xywh_list)))
+
+    @torch.no_grad()
+    def collect(self) -> List[PredictResult]:
+        """Wait for every submitted step; -> their results in submission order (and forget them)."""
+        if not self._pending:
+            return []
+        for p in self._pending:
+            p[1].synchronize()
+        results = [p[0] for p in self._pending]
+        flags = [p[2] for p in self._pending]
+        if any(f is not None for f in flags):
+            dev = self._pending[0][3].static_image.device
+            hit = torch.cat([f if f is not None else torch.zeros(1, dtype=torch.int32, device=dev) for f in flags]).cpu()
+            for i in hit.nonzero().flatten().tolist():
+                _, _, _, g, (frames, depth_gt, first_id, of, ox) = self._pending[i]
+                both = self.ends.ingest(frames)              # the slot's static input has long been overwritten: ingest again
+                out = g.rerun_on_bf16(both, of, ox) if g.objects is not None else g.rerun_on_bf16(both)
+                results[i] = self._finish(out, self.ends.ground_truth(depth_gt, self.B), first_id)
+                self.rerun_steps += 1
+            torch.cuda.current_stream(dev).synchronize()
+        self._pending = []
+        return results
+
+    def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
+        """The record table [N * B, 10] ([N * B, 16] with ``loss``) of collected results that carried ground truth."""
+        recs = [r.records for r in results if r.records is not None]
+        if not recs:
+            return torch.empty(0, len(RECORD_FIELDS) + (len(LOSS_FIELDS) if self.ends.loss else 0))
+        return torch.cat(recs, 0)
