@@ -323,6 +323,20 @@ int ocv_bin_head_folded_ws_fwd(const float* feat, int channels_last, const float
 int ocv_bin_head_fwd(const float* feat, int channels_last, const float* queries, long q_bs, int q_ld, const float* Wout,
                      const float* bout, const float* centers, float* depth, int B, int C, int Q, int n_bins, int P,
                      void* workspace, size_t workspace_bytes, ocv_stream_t stream);
+/* Per-pixel statistics of the SAME softmax, opt-in (the STATS instantiations of every kernel above): with p_k = softmax_k(logits),
+ * c_k = centers[b][k] and depth = sum_k p_k c_k as above,
+ *   var[b][p]  = sum_k p_k (c_k - depth)^2   (m^2; a negative rounding result is clamped to 0)
+ *   pmax[b][p] = max_k p_k                   (= 1 / sum_k exp(logit_k - max logit): what the online softmax carries)
+ * both [B][1][P] fp32, each nullable, at least one given; a non-finite pixel gives NaN in both, as in depth.  The moments are carried
+ * in fp64 about a per-image pivot, so var has no cancellation floor.  depth is bit-equal to ocv_bin_head_folded_ws_fwd's on the same
+ * route; channels_last takes all five codes, 2 (three-term bf16) needs partials of ocv_bin_head_stats_partials_bytes (B, P) bytes,
+ * 16-byte aligned (the float4 records + one fp64 moment record per image, half and pixel); the other codes ignore partials.  Under the
+ * two-level code 4 the bins left out add <= 8.5e-9 (max_depth - min_depth)^2 to var and <= 8.5e-9 relative to 1 / pmax.
+ * No allocation, no synchronisation (hipGraph-capturable); two calls give bit-equal output. */
+size_t ocv_bin_head_stats_partials_bytes(int B, int P);
+int ocv_bin_head_folded_stats_fwd(const float* feat, int channels_last, const float* Wf, const float* bout, const float* centers,
+                                  float* depth, int B, int C, int n_bins, int P, void* partials, size_t partials_bytes, float* var,
+                                  float* pmax, ocv_stream_t stream);
 
 /* 3 x 3 convolution, stride 1, zero padding 1, of an image with 1..4 channels into Cout channels (multiple of 4): exact fp32
  * FMA, raw result (no bias, no activation) as NHWC fp32 y [B][H][W][Cout].  x is addressed by element strides (batch,
@@ -666,6 +680,18 @@ int ocv_depth_ingest_fwd(const uint16_t* depth, long frame_stride, long row_stri
 int ocv_depth_finalize_fwd(const float* pred, const float* pred_mirror, int h, int w, float min_depth, float max_depth, int H, int W,
                            float* depth, uint16_t* depth_u16, float u16_scale, uint8_t* rgb8, const uint8_t* colormap, float vmin,
                            float colormap_scale, int B, ocv_stream_t stream);
+/* The same resize for the bin head's statistics.  The distribution predicted at an output pixel is the MIXTURE of its source
+ * distributions, weighted with the bilinear align_corners weights w_t of the depth map above (under flip-TTA: halved, over pred / var /
+ * pmax and the un-mirrored *_mirror maps).  With d_t the UNCLAMPED pred, m = sum_t w_t d_t:
+ *   depth_std  fp32 [B][1][H][W] = sqrt( sum_t w_t (var_t + (d_t - m)^2) )    (law of total variance: every term non-negative)
+ *   confidence fp32 [B][1][H][W] = sum_t w_t pmax_t
+ * nan -> max_depth - min_depth (depth_std), 0 (confidence); a NaN source pixel reaches every output pixel that has it as a tap, zero-weight
+ * taps included.  Each output nullable (at least one given); depth_std reads pred and var, confidence reads pmax -- maps that are not
+ * read may be null; with flip-TTA (any *_mirror given) every map that is read needs its mirror.  All maps [B][1][h][w].  One launch, the
+ * LDS tile staging and the vector / scalar store rules of ocv_depth_finalize_fwd; no allocation, no synchronisation; bit-equal on repeat. */
+int ocv_depth_finalize_stats_fwd(const float* pred, const float* pred_mirror, const float* var, const float* var_mirror,
+                                 const float* pmax, const float* pmax_mirror, int h, int w, float min_depth, float max_depth, int H, int W,
+                                 float* depth_std, float* confidence, int B, ocv_stream_t stream);
 
 /* Tail of mViT / ObjCAViT.forward + glue of AdaBins / GraphBins.forward in one launch (modules/miniViT.py:33-42, modules/AdaBins.py:79-83):
  *   y = raw [B][n_bins] (the regressor's last Linear) -> OCV_BINNORM_LINEAR: relu(y) + 0.1 | OCV_BINNORM_SIGMOID: sigmoid(y) |

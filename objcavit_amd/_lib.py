@@ -104,6 +104,9 @@ PROTOTYPES = {
     "ocv_bin_head_partials_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ocv_bin_head_folded_ws_fwd": (C.c_int, [_f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_void_p, C.c_size_t, _stream]),
+    "ocv_bin_head_stats_partials_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ocv_bin_head_folded_stats_fwd": (C.c_int, [_f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_size_t, _f32p, _f32p, _stream]),
     "ocv_bin_head_fwd": (C.c_int, [_f32p, C.c_int, _f32p, C.c_long, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, _stream]),
     "ocv_depthwise_conv_fwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p] + [C.c_int] * 11 + [_stream]),
@@ -123,6 +126,8 @@ PROTOTYPES = {
                                        C.c_int, _stream]),
     "ocv_depth_finalize_fwd": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, C.c_void_p, C.c_float,
                                          _u8p, _u8p, C.c_float, C.c_float, C.c_int, _stream]),
+    "ocv_depth_finalize_stats_fwd": (C.c_int, [_f32p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_int,
+                                               _stream]),
     "ocv_conv3x3_few_channels_fwd": (C.c_int, [_f32p, C.c_long, C.c_long, C.c_long, C.c_long, _f32p, _f32p] + [C.c_int] * 5 + [_stream]),
     "ocv_stem_conv_fwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p] + [C.c_int] * 12 + [_stream]),
     "ocv_pointwise_packed_weight_elems": (C.c_size_t, [C.c_int, C.c_int]),

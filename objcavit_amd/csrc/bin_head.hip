@@ -31,6 +31,37 @@ constexpr int NB = 256;        // bins
 constexpr int WLD = CH + 1;
 constexpr int TP = 128;        // pixels per workgroup tile
 
+// STATS (opt-in, every kernel below): besides depth = sum p_k c_k, two more numbers of the same softmax per pixel --
+//   var  = sum_k p_k (c_k - depth)^2   (m^2, clamped at 0)        pmax = max_k p_k = 1 / sum_k exp(x_k - max x)
+// The moments are carried about a per-image pivot c0 = (c_0 + c_255) / 2 in fp64: L = sum e_k, S1 = sum e_k q_k, S2 = sum e_k q_k^2 with
+// q_k = c_k - c0 (q_k and q_k^2 staged in LDS as doubles), rescaled by the online softmax's alpha like the fp32 sums, and
+// var = S2 / L - (S1 / L)^2 is formed in fp64 at the end.  In fp32 that difference loses eps * (c - c0)^2 (2e-6 m^2 over NYU's range, the
+// whole answer under a near-one-hot softmax); in fp64 what is left is the error of the exponentials themselves, which scales with var.
+// Cost: one convert, one add and two FMAs in fp64 per bin, unpacked, beside the packed fp32 arithmetic (about 2.5 slots per bin): what
+// that does to the launch is measured, not assumed (profiles/bin_stats.txt, step b).  The fp32 statements that form
+// depth are untouched, so depth is bit-equal with and without STATS, and the STATS = false instantiations are the kernels as they were
+// (every added statement sits under `if constexpr (STATS)`; the extra kernel argument is an empty struct).
+template <bool STATS> struct StatsOut {};
+template <> struct StatsOut<true> { float *var, *pmax; };          // [B][1][P] each, either may be null
+template <bool STATS> struct StatsPart {};                         // the split-3 halves' fp64 moment records
+template <> struct StatsPart<true> { double* rec; };
+
+__device__ __forceinline__ double xor32_sum_f64(double v) { return v + __shfl_xor(v, 32, 64); }
+
+// stage q_k = c_k - c0 and q_k^2 of image b's centres (threads 0 .. 255)
+__device__ __forceinline__ void stage_pivot(double* qd, const float* __restrict__ cb, int k) {
+  const double q = (double)cb[k] - 0.5 * ((double)cb[0] + (double)cb[NB - 1]);
+  qd[k] = q;
+  qd[NB + k] = q * q;
+}
+
+__device__ __forceinline__ void store_stats(const StatsOut<true>& so, long i, double L, double S1, double S2) {
+  const double mu = S1 / L;
+  const float v = (float)(S2 / L - mu * mu);
+  if (so.var != nullptr) so.var[i] = v < 0.f ? 0.f : v;           // (a NaN stays a NaN)
+  if (so.pmax != nullptr) so.pmax[i] = (float)(1.0 / L);           // the largest bin's exponential is exp(0) = 1
+}
+
 // B operand of one 32-pixel wavefront tile: 64 VGPRs, lane = (pixel l31, k-slot hh).
 // The K order of an MFMA chain is free as long as A and B agree, so it is chosen per layout:
 //   NCHW  feat[c][p]: step s, slot hh <-> channel 2s + hh   (128-B coalesced run per half-wave per channel)
@@ -55,15 +86,16 @@ __device__ __forceinline__ void load_pixels(float (&bf)[CH / 2], const float* __
 template <bool NHWC>
 __device__ __forceinline__ constexpr int a_col(int s, int hh) { return NHWC ? 64 * hh + s : 2 * s + hh; }
 
-template <bool NHWC>
+template <bool NHWC, bool STATS>
 __global__ __launch_bounds__(256) void bin_head_kernel(const float* __restrict__ feat, const float* __restrict__ Wf,
                                                        const float* __restrict__ bout,
                                                        const float* __restrict__ centers, float* __restrict__ depth,
-                                                       long P, int ntiles) {
+                                                       long P, int ntiles, StatsOut<STATS> so) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Wl = lds;                  // [256][129]
   float* bl = Wl + NB * WLD;        // [256]
   float* cl = bl + NB;              // [256]
+  double* qd = reinterpret_cast<double*>(cl + NB);     // [2][256] (STATS)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
@@ -79,6 +111,7 @@ __global__ __launch_bounds__(256) void bin_head_kernel(const float* __restrict__
   }
   bl[tid] = bout[tid];
   cl[tid] = centers[(long)b * NB + tid];
+  if constexpr (STATS) stage_pivot(qd, centers + (long)b * NB, tid);
   __syncthreads();
 
   float cur[CH / 2], nxt[CH / 2];
@@ -96,6 +129,7 @@ __global__ __launch_bounds__(256) void bin_head_kernel(const float* __restrict__
     }
 
     float m_run = -__builtin_inff(), l_half = 0.f, d_half = 0.f;
+    double Ld = 0.0, S1 = 0.0, S2 = 0.0;
 #pragma unroll 1
     for (int t = 0; t < NB / 32; ++t) {
       f32x16 acc = {0};
@@ -113,11 +147,21 @@ __global__ __launch_bounds__(256) void bin_head_kernel(const float* __restrict__
       const float m_new = fmaxf(m_run, tmax);
       const float alpha = fast_exp(m_run - m_new);
       float ps = 0.f, ds = 0.f;
+      if constexpr (STATS) {
+        const double ad = (double)alpha;
+        Ld *= ad; S1 *= ad; S2 *= ad;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float pr = fast_exp(acc[r] - m_new);
         ps += pr;
         ds += pr * cl[t * 32 + acc_row(r, hh)];
+        if constexpr (STATS) {
+          const double pd = (double)pr;
+          Ld += pd;
+          S1 += pd * qd[t * 32 + acc_row(r, hh)];
+          S2 += pd * qd[NB + t * 32 + acc_row(r, hh)];
+        }
       }
       l_half = l_half * alpha + ps;
       d_half = d_half * alpha + ds;
@@ -125,6 +169,10 @@ __global__ __launch_bounds__(256) void bin_head_kernel(const float* __restrict__
     }
     const float l = xor32_sum(l_half), d = xor32_sum(d_half);
     if (hh == 0 && pix < P) depth[(long)b * P + pix] = d / l;
+    if constexpr (STATS) {
+      Ld = xor32_sum_f64(Ld); S1 = xor32_sum_f64(S1); S2 = xor32_sum_f64(S2);
+      if (hh == 0 && pix < P) store_stats(so, (long)b * P + pix, Ld, S1, S2);
+    }
 
     if (tn < ntiles) {
 #pragma unroll
@@ -166,14 +214,18 @@ __device__ __forceinline__ void bh_split8x3(const float4 u, const float4 v, bh_b
   }
 }
 
+// STATS: the half's fp64 moments (L, S1, S2, about the IMAGE's pivot: both halves use the same) go to a second record array behind the
+// float4 records, 32 bytes per (image, half, pixel)
+template <bool STATS>
 __global__ __launch_bounds__(512, 2) void bin_head_split3_kernel(const float* __restrict__ feat, const float* __restrict__ Wf,
                                                                  const float* __restrict__ bout,
                                                                  const float* __restrict__ centers, float* __restrict__ part,
-                                                                 long P, int ntiles) {
+                                                                 long P, int ntiles, StatsPart<STATS> sp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __bf16* wfrag = reinterpret_cast<__bf16*>(lds);           // [4 bin tiles][8 K steps][h, m, l][64 lanes][8]
   float* bl = lds + (HB * CH * 3 * 2) / 4;                   // [128]
   float* cl = bl + HB;                                       // [128]
+  double* qd = reinterpret_cast<double*>(cl + HB);           // [2][256], the first 128 of each row used (STATS)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
@@ -193,6 +245,12 @@ __global__ __launch_bounds__(512, 2) void bin_head_split3_kernel(const float* __
   if (tid < HB) {
     bl[tid] = bout[half * HB + tid];
     cl[tid] = centers[(long)b * NB + half * HB + tid];
+    if constexpr (STATS) {
+      const float* cb = centers + (long)b * NB;
+      const double q = (double)cb[half * HB + tid] - 0.5 * ((double)cb[0] + (double)cb[NB - 1]);
+      qd[tid] = q;
+      qd[NB + tid] = q * q;
+    }
   }
   __syncthreads();
 
@@ -216,6 +274,7 @@ __global__ __launch_bounds__(512, 2) void bin_head_split3_kernel(const float* __
     if (tn < ntiles) load_px(nxt, (long)tn * TP3 + wave * 32 + l31);   // in flight under this tile's 192 MFMAs
 
     float m_run = -__builtin_inff(), l_half = 0.f, d_half = 0.f;
+    double Ld = 0.0, S1 = 0.0, S2 = 0.0;
 #pragma unroll 1
     for (int t = 0; t < HB / 32; ++t) {
       f32x16 acc = {0};
@@ -242,11 +301,21 @@ __global__ __launch_bounds__(512, 2) void bin_head_split3_kernel(const float* __
       const float m_new = fmaxf(m_run, tmax);
       const float alpha = fast_exp(m_run - m_new);
       float ps = 0.f, ds = 0.f;
+      if constexpr (STATS) {
+        const double ad = (double)alpha;
+        Ld *= ad; S1 *= ad; S2 *= ad;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float pr = fast_exp(acc[r] - m_new);
         ps += pr;
         ds += pr * cl[t * 32 + acc_row(r, hh)];
+        if constexpr (STATS) {
+          const double pd = (double)pr;
+          Ld += pd;
+          S1 += pd * qd[t * 32 + acc_row(r, hh)];
+          S2 += pd * qd[NB + t * 32 + acc_row(r, hh)];
+        }
       }
       l_half = l_half * alpha + ps;
       d_half = d_half * alpha + ds;
@@ -256,6 +325,14 @@ __global__ __launch_bounds__(512, 2) void bin_head_split3_kernel(const float* __
     if (hh == 0 && pix < P) {
       float* o = part + (((long)b * 2 + half) * P + pix) * 4;
       *reinterpret_cast<float4*>(o) = make_float4(m_run, l, d, 0.f);
+    }
+    if constexpr (STATS) {
+      Ld = xor32_sum_f64(Ld); S1 = xor32_sum_f64(S1); S2 = xor32_sum_f64(S2);
+      if (hh == 0 && pix < P) {
+        double* o = sp.rec + (((long)b * 2 + half) * P + pix) * 4;
+        *reinterpret_cast<double2*>(o) = make_double2(Ld, S1);
+        o[2] = S2;
+      }
     }
   }
 }
@@ -319,11 +396,14 @@ typedef float bh_f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 bh_h16x2 __attribute__((ext_vector_type(2)));
 constexpr float BH_SKIP_T = 24.0f * 1.44269504088896340736f;     // T in the kernel's base-2 logits
 
-template <bool TWO_LEVEL>
+// STATS: the dense form walks its tiles one at a time like the two-level form's exact pass (MFMAs, then the softmax arithmetic: the
+// software pipeline's second accumulator pair and the fp64 moments do not fit 256 registers together); same statements per tile, so
+// depth keeps its bits.
+template <bool TWO_LEVEL, bool STATS>
 __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __restrict__ feat, const float* __restrict__ Wf,
                                                              const float* __restrict__ bout,
                                                              const float* __restrict__ centers, float* __restrict__ depth,
-                                                             long P, int ntiles) {
+                                                             long P, int ntiles, StatsOut<STATS> so) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   _Float16* wfrag = reinterpret_cast<_Float16*>(lds);       // [8 bin tiles][8 K steps][hi, lo'][64 lanes][8]
   float* bl = lds + (NB * CH * 2 * 2) / 4;                   // [256]  bias * log2(e)
@@ -337,6 +417,7 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
   const float* wb = Wf + (long)b * NB * CH;
 
   unsigned* wn2 = reinterpret_cast<unsigned*>(cl + NB);     // [1] the largest squared row norm of Wf[b] log2(e), as bits (TWO_LEVEL)
+  double* qd = reinterpret_cast<double*>(cl + NB + 4);      // [2][256] (STATS)
   if (TWO_LEVEL) {
     if (tid == 0) *wn2 = 0u;
     __syncthreads();
@@ -361,6 +442,7 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
   if (tid < NB) {
     bl[tid] = bout[tid] * LOG2E;
     cl[tid] = centers[(long)b * NB + tid];
+    if constexpr (STATS) stage_pivot(qd, centers + (long)b * NB, tid);
   }
   __syncthreads();
 
@@ -415,6 +497,7 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
     };
     float m_run = -__builtin_inff();                         // online softmax over this lane's 16 bins per tile, in base 2
     bh_f32x2 l2 = {0.f, 0.f}, d2 = {0.f, 0.f};               // (its pixel's other 16 bins sit in lane ^ 32)
+    double Ld = 0.0, S1 = 0.0, S2 = 0.0;
     // softmax arithmetic of bin tile t; afterwards a1 holds the bias of tile tb (the accumulator's next initial value)
     auto softmax_tile = [&](int t, f32x16& a1, const f32x16& a2, int tb) {
       bh_f32x2 lg[8];
@@ -430,6 +513,10 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
       const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
       const float* cp = cl + t * 32 + 4 * hh;
       bh_f32x2 ps = {0.f, 0.f}, ds = {0.f, 0.f};
+      if constexpr (STATS) {
+        const double ad = (double)alpha;
+        Ld *= ad; S1 *= ad; S2 *= ad;
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 c4 = *reinterpret_cast<const f32x4*>(cp + 8 * g);
@@ -439,6 +526,15 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
           const bh_f32x2 pr = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
           ps += pr;
           ds += pr * bh_f32x2{c4[2 * j], c4[2 * j + 1]};
+          if constexpr (STATS) {
+            const double* qp = qd + t * 32 + 4 * hh;
+            const double2 q = *reinterpret_cast<const double2*>(qp + 8 * g + 2 * j);
+            const double2 q2 = *reinterpret_cast<const double2*>(qp + NB + 8 * g + 2 * j);
+            const double p0 = (double)pr.x, p1 = (double)pr.y;
+            Ld += p0; Ld += p1;
+            S1 += p0 * q.x; S1 += p1 * q.y;
+            S2 += p0 * q2.x; S2 += p1 * q2.y;
+          }
         }
       }
       l2 = l2 * alpha + ps;
@@ -516,6 +612,13 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
         mma_tile(t, A1, A2);
         softmax_tile(t, A1, A2, t);
       }
+    } else if constexpr (STATS) {
+#pragma unroll 1
+      for (int t = 0; t < NB / 32; ++t) {
+        fetch_bias(t, A1);
+        mma_tile(t, A1, A2);
+        softmax_tile(t, A1, A2, t);
+      }
     } else {
     fetch_bias(0, A1);
     fetch_bias(1, B1);
@@ -542,6 +645,10 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
 #undef BH_INTERLEAVE
     const float l = xor32_sum(l2.x + l2.y), d = xor32_sum(d2.x + d2.y);
     if (hh == 0 && pix < P) depth[(long)b * P + pix] = d / l;
+    if constexpr (STATS) {
+      Ld = xor32_sum_f64(Ld); S1 = xor32_sum_f64(S1); S2 = xor32_sum_f64(S2);
+      if (hh == 0 && pix < P) store_stats(so, (long)b * P + pix, Ld, S1, S2);
+    }
 
     if (tn < ntiles) {
 #pragma unroll
@@ -551,8 +658,9 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
 }
 
 // depth = (d0 e0 + d1 e1) / (l0 e0 + l1 e1),  e_i = exp(m_i - max(m0, m1)): the online-softmax merge of the two halves
+template <bool STATS>
 __global__ __launch_bounds__(256) void bin_head_combine_kernel(const float* __restrict__ part, float* __restrict__ depth, long P,
-                                                               long total) {
+                                                               long total, StatsPart<STATS> sp, StatsOut<STATS> so) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;     // b * P + pixel
   if (i >= total) return;
   const long b = i / P, px = i - b * P;
@@ -561,6 +669,12 @@ __global__ __launch_bounds__(256) void bin_head_combine_kernel(const float* __re
   const float m = fmaxf(a.x, c.x);
   const float ea = fast_exp(a.x - m), ec = fast_exp(c.x - m);
   depth[i] = (a.z * ea + c.z * ec) / (a.y * ea + c.y * ec);
+  if constexpr (STATS) {
+    const double* sa = sp.rec + ((b * 2 + 0) * P + px) * 4;
+    const double* sc = sp.rec + ((b * 2 + 1) * P + px) * 4;
+    const double da = (double)ea, dc = (double)ec;
+    store_stats(so, i, sa[0] * da + sc[0] * dc, sa[1] * da + sc[1] * dc, sa[2] * da + sc[2] * dc);
+  }
 }
 
 // ram[b][q][p] = sum_c queries[b][q][c] * feat[b][c][p]
@@ -667,15 +781,15 @@ extern "C" int ocv_bin_head_folded_fwd(const float* feat, int channels_last, con
   OCV_CHECK_ARG(!channels_last || ocv_aligned16(feat), "ocv_bin_head_folded_fwd: channels_last map must be 16-byte aligned");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)bin_head_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)bin_head_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   if (channels_last == 3 || channels_last == 4) {            // two-term fp16 split, all 256 bins per workgroup; 4 = two-level logits (the default route)
     static bool attr3 = false;
     if (!attr3) {
-      (void)hipFuncSetAttribute((const void*)bin_head_h2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)bin_head_h2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void*)bin_head_h2_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void*)bin_head_h2_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr3 = true;
     }
     const int nt = ocv_cdiv(P, TP3);
@@ -684,11 +798,11 @@ extern "C" int ocv_bin_head_folded_fwd(const float* feat, int channels_last, con
     if (perh < 1) perh = 1;
     const size_t ldsh = (size_t)NB * CH * 2 * 2 + 2 * NB * sizeof(float) + 16;
     if (channels_last == 4)
-      hipLaunchKernelGGL(bin_head_h2_kernel<true>, dim3(perh, B), dim3(512), ldsh, (hipStream_t)stream, feat, Wf, bout, centers,
-                         depth, (long)P, nt);
+      hipLaunchKernelGGL((bin_head_h2_kernel<true, false>), dim3(perh, B), dim3(512), ldsh, (hipStream_t)stream, feat, Wf, bout, centers,
+                         depth, (long)P, nt, StatsOut<false>{});
     else
-      hipLaunchKernelGGL(bin_head_h2_kernel<false>, dim3(perh, B), dim3(512), ldsh, (hipStream_t)stream, feat, Wf, bout, centers,
-                         depth, (long)P, nt);
+      hipLaunchKernelGGL((bin_head_h2_kernel<false, false>), dim3(perh, B), dim3(512), ldsh, (hipStream_t)stream, feat, Wf, bout, centers,
+                         depth, (long)P, nt, StatsOut<false>{});
     OCV_CHECK_LAUNCH("ocv_bin_head_folded_fwd(h2)");
     return 0;
   }
@@ -697,11 +811,11 @@ extern "C" int ocv_bin_head_folded_fwd(const float* feat, int channels_last, con
   const size_t lds = (size_t)(NB * WLD + 2 * NB) * sizeof(float);
   // NHWC maps: channels_last == 1 -> exact fp32 MFMA; NCHW maps (0): the same kernel reading planes
   if (channels_last)
-    hipLaunchKernelGGL(bin_head_kernel<true>, dim3(per, B), dim3(256), lds, (hipStream_t)stream, feat, Wf, bout,
-                       centers, depth, (long)P, ntiles);
+    hipLaunchKernelGGL((bin_head_kernel<true, false>), dim3(per, B), dim3(256), lds, (hipStream_t)stream, feat, Wf, bout,
+                       centers, depth, (long)P, ntiles, StatsOut<false>{});
   else
-    hipLaunchKernelGGL(bin_head_kernel<false>, dim3(per, B), dim3(256), lds, (hipStream_t)stream, feat, Wf, bout,
-                       centers, depth, (long)P, ntiles);
+    hipLaunchKernelGGL((bin_head_kernel<false, false>), dim3(per, B), dim3(256), lds, (hipStream_t)stream, feat, Wf, bout,
+                       centers, depth, (long)P, ntiles, StatsOut<false>{});
   OCV_CHECK_LAUNCH("ocv_bin_head_folded_fwd");
   return 0;
 }
@@ -718,7 +832,7 @@ extern "C" int ocv_bin_head_folded_ws_fwd(const float* feat, int channels_last, 
   OCV_CHECK_ARG(partials_bytes >= ocv_bin_head_partials_bytes(B, P), "ocv_bin_head_folded_ws_fwd: partials buffer too small");
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)bin_head_split3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_split3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   const int ntiles = ocv_cdiv(P, TP3);
@@ -726,13 +840,82 @@ extern "C" int ocv_bin_head_folded_ws_fwd(const float* feat, int channels_last, 
   if (per > ntiles) per = ntiles;
   if (per < 1) per = 1;
   const size_t lds3 = (size_t)HB * CH * 3 * 2 + 2 * HB * sizeof(float);
-  hipLaunchKernelGGL(bin_head_split3_kernel, dim3(per, 2, B), dim3(512), lds3, (hipStream_t)stream, feat, Wf, bout, centers,
-                     (float*)partials, (long)P, ntiles);
+  hipLaunchKernelGGL(bin_head_split3_kernel<false>, dim3(per, 2, B), dim3(512), lds3, (hipStream_t)stream, feat, Wf, bout, centers,
+                     (float*)partials, (long)P, ntiles, StatsPart<false>{});
   OCV_CHECK_LAUNCH("ocv_bin_head_folded_ws_fwd(halves)");
   const long total = (long)B * P;
-  hipLaunchKernelGGL(bin_head_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const float*)partials, depth, (long)P, total);
+  hipLaunchKernelGGL(bin_head_combine_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)partials, depth, (long)P, total, StatsPart<false>{}, StatsOut<false>{});
   OCV_CHECK_LAUNCH("ocv_bin_head_folded_ws_fwd(combine)");
+  return 0;
+}
+
+extern "C" size_t ocv_bin_head_stats_partials_bytes(int B, int P) {
+  if (B < 1 || P < 1) return 0;
+  return (size_t)B * 2 * P * (4 * sizeof(float) + 4 * sizeof(double));       // the float4 records, then the fp64 moment records
+}
+
+// depth as ocv_bin_head_folded_ws_fwd forms it on the same route (bit-equal) + var / pmax: the STATS instantiations
+extern "C" int ocv_bin_head_folded_stats_fwd(const float* feat, int channels_last, const float* Wf, const float* bout,
+                                             const float* centers, float* depth, int B, int C, int n_bins, int P, void* partials,
+                                             size_t partials_bytes, float* var, float* pmax, ocv_stream_t stream) {
+  OCV_CHECK_ARG(feat && Wf && bout && centers && depth, "ocv_bin_head_folded_stats_fwd: null pointer");
+  OCV_CHECK_ARG(var || pmax, "ocv_bin_head_folded_stats_fwd: null pointer (at least one of var, pmax must be given)");
+  OCV_CHECK_ARG(C == CH && n_bins == NB, "ocv_bin_head_folded_stats_fwd: needs C = %d, n_bins = %d", CH, NB);
+  OCV_CHECK_ARG(B >= 1 && B <= 65535 && P >= 1 && ocv_aligned16(Wf), "ocv_bin_head_folded_stats_fwd: bad sizes / alignment");
+  OCV_CHECK_ARG(channels_last >= 0 && channels_last <= 4, "ocv_bin_head_folded_stats_fwd: channels_last must be 0 (NCHW, exact fp32), 1 (NHWC, exact fp32), 2 (NHWC, three-term bf16), 3 (NHWC, two-term fp16) or 4 (the same with two-level logits)");
+  OCV_CHECK_ARG(!channels_last || ocv_aligned16(feat), "ocv_bin_head_folded_stats_fwd: channels_last map must be 16-byte aligned");
+  OCV_CHECK_ARG(channels_last != 2 || (partials && ocv_aligned16(partials) && partials_bytes >= ocv_bin_head_stats_partials_bytes(B, P)),
+                "ocv_bin_head_folded_stats_fwd: the three-term route needs a 16-byte aligned partials buffer of ocv_bin_head_stats_partials_bytes");
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)bin_head_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_h2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_h2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)bin_head_split3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  const StatsOut<true> so{var, pmax};
+  const size_t qbytes = 2 * NB * sizeof(double);             // the pivot tables behind each kernel's own LDS
+  hipStream_t st = (hipStream_t)stream;
+  if (channels_last == 3 || channels_last == 4) {            // grids and LDS as in ocv_bin_head_folded_fwd
+    const int nt = ocv_cdiv(P, TP3);
+    int perh = (256 + B - 1) / B;
+    if (perh > nt) perh = nt;
+    if (perh < 1) perh = 1;
+    const size_t ldsh = (size_t)NB * CH * 2 * 2 + 2 * NB * sizeof(float) + 16 + qbytes;
+    if (channels_last == 4)
+      hipLaunchKernelGGL((bin_head_h2_kernel<true, true>), dim3(perh, B), dim3(512), ldsh, st, feat, Wf, bout, centers, depth, (long)P, nt, so);
+    else
+      hipLaunchKernelGGL((bin_head_h2_kernel<false, true>), dim3(perh, B), dim3(512), ldsh, st, feat, Wf, bout, centers, depth, (long)P, nt, so);
+    OCV_CHECK_LAUNCH("ocv_bin_head_folded_stats_fwd(h2)");
+    return 0;
+  }
+  if (channels_last == 2) {                                  // as in ocv_bin_head_folded_ws_fwd
+    const int ntiles = ocv_cdiv(P, TP3);
+    int per = (256 + 2 * B - 1) / (2 * B);
+    if (per > ntiles) per = ntiles;
+    if (per < 1) per = 1;
+    const size_t lds3 = (size_t)HB * CH * 3 * 2 + 2 * HB * sizeof(float) + qbytes;
+    const StatsPart<true> sp{reinterpret_cast<double*>((char*)partials + (size_t)B * 2 * P * 4 * sizeof(float))};
+    hipLaunchKernelGGL(bin_head_split3_kernel<true>, dim3(per, 2, B), dim3(512), lds3, st, feat, Wf, bout, centers, (float*)partials,
+                       (long)P, ntiles, sp);
+    OCV_CHECK_LAUNCH("ocv_bin_head_folded_stats_fwd(halves)");
+    const long total = (long)B * P;
+    hipLaunchKernelGGL(bin_head_combine_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)partials,
+                       depth, (long)P, total, sp, so);
+    OCV_CHECK_LAUNCH("ocv_bin_head_folded_stats_fwd(combine)");
+    return 0;
+  }
+  const int ntiles = ocv_cdiv(P, TP);
+  const int per = blocks_per_image(B, ntiles);
+  const size_t lds = (size_t)(NB * WLD + 2 * NB) * sizeof(float) + qbytes;
+  if (channels_last)
+    hipLaunchKernelGGL((bin_head_kernel<true, true>), dim3(per, B), dim3(256), lds, st, feat, Wf, bout, centers, depth, (long)P, ntiles, so);
+  else
+    hipLaunchKernelGGL((bin_head_kernel<false, true>), dim3(per, B), dim3(256), lds, st, feat, Wf, bout, centers, depth, (long)P, ntiles, so);
+  OCV_CHECK_LAUNCH("ocv_bin_head_folded_stats_fwd");
   return 0;
 }
 

@@ -160,6 +160,146 @@ __global__ __launch_bounds__(256) void depth_finalize_kernel(FinArgs p) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// The same resize for the bin head's per-pixel statistics (csrc/bin_head.hip, STATS): the distribution predicted at an output pixel
+// is the MIXTURE of its source distributions with the bilinear weights above (halved over the map and the un-mirrored mirror map
+// under flip-TTA).  With d_t, var_t, pmax_t the sources' mean (UNCLAMPED), variance and peak probability and w_t their weights:
+//   m = sum w_t d_t     var = sum w_t (var_t + (d_t - m)^2)   (law of total variance)     depth_std = sqrt(var)     confidence = sum w_t pmax_t
+// nan -> max_depth - min_depth (std), 0 (confidence).  The TTA pair of a source pixel is merged first -- mean (a + b) / 2, variance
+// (var_a + var_b) / 2 + (a - b)^2 / 4, the same law applied to the inner mixture: every term stays non-negative -- so a tile stages three
+// numbers per source pixel.  The weights are the depth kernel's fp32 weights, statement for statement; the sums over the taps run in
+// fp64 (a few operations per pixel under a launch bound by its stores).
+// ---------------------------------------------------------------------------
+struct FinStatsArgs {
+  const float *pred, *mirror, *var, *var_mirror, *pmax, *pmax_mirror;      // var / pmax (and their mirrors) null when their output is
+  float* std_out;                     // [B][1][H][W] or null
+  float* conf;                        // [B][1][H][W] or null
+  int h, w, H, W, B;
+  float sh, sw, span;
+};
+
+struct Src3 { float mean, var, peak; };
+
+__device__ __forceinline__ Src3 tap3(const FinStatsArgs& p, long base, int y, int x) {
+  const long i = base + y * p.w + x, j = base + y * p.w + (p.w - 1 - x);
+  Src3 r{0.f, 0.f, 0.f};
+  const bool tta = p.mirror != nullptr;
+  if (p.std_out != nullptr) {
+    const double a = p.pred[i], va = p.var[i];
+    if (tta) {
+      const double b = p.mirror[j], vb = p.var_mirror[j], df = a - b;
+      r.mean = (float)(0.5 * (a + b));
+      r.var = (float)(0.5 * (va + vb) + 0.25 * df * df);
+    } else {
+      r.mean = (float)a;
+      r.var = (float)va;
+    }
+  }
+  if (p.conf != nullptr) r.peak = tta ? 0.5f * (p.pmax[i] + p.pmax_mirror[j]) : p.pmax[i];
+  return r;
+}
+
+struct Fin2 { float sd, cf; };
+
+template <typename Fetch>
+__device__ __forceinline__ Fin2 final_stats(const FinStatsArgs& p, Fetch fetch, int Y, int X) {
+  double var, cf;
+  if (p.h == p.H && p.w == p.W) {
+    const Src3 s = fetch(Y, X);
+    const double e = (double)s.mean - (double)s.mean;            // 0, or NaN for a non-finite mean: m = d_t here, and (d_t - m)^2 keeps it
+    var = s.var + e * e; cf = s.peak;
+  } else {
+    const float sy = p.sh * Y, sx = p.sw * X;
+    const int ya = min((int)sy, p.h - 1), xa = min((int)sx, p.w - 1);
+    const int yb = ya + (ya < p.h - 1 ? 1 : 0), xb = xa + (xa < p.w - 1 ? 1 : 0);
+    const float h1 = sy - (float)ya, h0 = 1.0f - h1, w1 = sx - (float)xa, w0 = 1.0f - w1;
+    const Src3 s[4] = {fetch(ya, xa), fetch(ya, xb), fetch(yb, xa), fetch(yb, xb)};
+    const double wt[4] = {(double)h0 * w0, (double)h0 * w1, (double)h1 * w0, (double)h1 * w1};
+    double m = 0.0;
+    cf = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { m += wt[t] * s[t].mean; cf += wt[t] * s[t].peak; }      // (all four terms always: 0 * NaN = NaN, as in the depth map)
+    var = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { const double e = s[t].mean - m; var += wt[t] * (s[t].var + e * e); }
+  }
+  Fin2 r;
+  r.sd = (float)__builtin_sqrt(var);
+  r.cf = (float)cf;
+  if (r.sd != r.sd) r.sd = p.span;
+  if (r.cf != r.cf) r.cf = 0.f;
+  return r;
+}
+
+__device__ __forceinline__ void store8f(float* dst, long o, const float (&v)[8]) {
+  *reinterpret_cast<float4*>(dst + o) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(dst + o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+constexpr int STAGE_PIXELS = STAGE_FLOATS;       // the same source window as the depth kernel's tile, three numbers per pixel
+
+__global__ __launch_bounds__(256) void depth_finalize_stats_tile_kernel(FinStatsArgs p, int tiles_x) {
+  __shared__ Src3 src[STAGE_PIXELS];
+  const int tid = threadIdx.x;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const long base = (long)blockIdx.y * p.h * p.w;
+  const int Y0 = ty * TILE_H, X0 = tx * TILE_W;
+  const int Yl = min(Y0 + TILE_H, p.H) - 1, Xl = min(X0 + TILE_W, p.W) - 1;
+  const int r0 = min((int)(p.sh * Y0), p.h - 1), r1 = min(min((int)(p.sh * Yl), p.h - 1) + 1, p.h - 1);
+  const int c0 = min((int)(p.sw * X0), p.w - 1), c1 = min(min((int)(p.sw * Xl), p.w - 1) + 1, p.w - 1);
+  const int nr = r1 - r0 + 1, nc = c1 - c0 + 1;
+  const bool staged = nr * nc <= STAGE_PIXELS;                   // uniform over the workgroup
+  if (staged) {
+    for (int i = tid; i < nr * nc; i += 256) {
+      const int r = i / nc, c = i - r * nc;
+      src[i] = tap3(p, base, r0 + r, c0 + c);
+    }
+  }
+  __syncthreads();
+  const int Y = Y0 + (tid >> 4), X = X0 + ((tid & 15) << 3);
+  if (Y >= p.H || X >= p.W) return;
+  float sd[8], cf[8];
+  if (staged) {
+    auto fetch = [&](int y, int x) { return src[(y - r0) * nc + (x - c0)]; };
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const Fin2 f = final_stats(p, fetch, Y, X + i); sd[i] = f.sd; cf[i] = f.cf; }
+  } else {
+    auto fetch = [&](int y, int x) { return tap3(p, base, y, x); };
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const Fin2 f = final_stats(p, fetch, Y, X + i); sd[i] = f.sd; cf[i] = f.cf; }
+  }
+  const long o = (long)blockIdx.y * p.H * p.W + (long)Y * p.W + X;
+  if (p.std_out != nullptr) store8f(p.std_out, o, sd);
+  if (p.conf != nullptr) store8f(p.conf, o, cf);
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void depth_finalize_stats_kernel(FinStatsArgs p) {
+  const long P = (long)p.H * p.W;
+  const long groups = P / V, total = groups * p.B;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    const long b = t / groups, pix0 = (t - b * groups) * V;
+    const long base = b * (long)p.h * p.w;
+    auto fetch = [&](int y, int x) { return tap3(p, base, y, x); };
+    int Y = (int)(pix0 / p.W), X = (int)(pix0 - (long)Y * p.W);
+    float sd[V], cf[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const Fin2 f = final_stats(p, fetch, Y, X);
+      sd[i] = f.sd; cf[i] = f.cf;
+      if (++X == p.W) { X = 0; ++Y; }
+    }
+    const long o = b * P + pix0;
+    if constexpr (V == 8) {
+      if (p.std_out != nullptr) store8f(p.std_out, o, sd);
+      if (p.conf != nullptr) store8f(p.conf, o, cf);
+    } else {
+      if (p.std_out != nullptr) p.std_out[o] = sd[0];
+      if (p.conf != nullptr) p.conf[o] = cf[0];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int ocv_depth_finalize_fwd(const float* pred, const float* pred_mirror, int h, int w, float min_depth, float max_depth,
@@ -192,5 +332,39 @@ extern "C" int ocv_depth_finalize_fwd(const float* pred, const float* pred_mirro
     else hipLaunchKernelGGL(depth_finalize_kernel<1>, dim3((int)grid), dim3(256), 0, st, a);
   }
   OCV_CHECK_LAUNCH("ocv_depth_finalize_fwd");
+  return 0;
+}
+
+extern "C" int ocv_depth_finalize_stats_fwd(const float* pred, const float* pred_mirror, const float* var, const float* var_mirror,
+                                            const float* pmax, const float* pmax_mirror, int h, int w, float min_depth, float max_depth,
+                                            int H, int W, float* depth_std, float* confidence, int B, ocv_stream_t stream) {
+  OCV_CHECK_ARG(depth_std || confidence, "ocv_depth_finalize_stats_fwd: null pointer (at least one of depth_std, confidence must be given)");
+  OCV_CHECK_ARG(!depth_std || (pred && var), "ocv_depth_finalize_stats_fwd: null pointer (depth_std needs pred and var)");
+  OCV_CHECK_ARG(!confidence || pmax, "ocv_depth_finalize_stats_fwd: null pointer (confidence needs pmax)");
+  const bool tta = pred_mirror || var_mirror || pmax_mirror;
+  OCV_CHECK_ARG(!tta || ((!depth_std || (pred_mirror && var_mirror)) && (!confidence || pmax_mirror)),
+                "ocv_depth_finalize_stats_fwd: null pointer (with flip-TTA every map that is read needs its mirror)");
+  OCV_CHECK_ARG(B >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "ocv_depth_finalize_stats_fwd: bad sizes (B, h, w, H, W must be >= 1)");
+  OCV_CHECK_ARG(min_depth < max_depth, "ocv_depth_finalize_stats_fwd: min_depth must be below max_depth");
+  OCV_CHECK_ARG((reinterpret_cast<uintptr_t>(depth_std) & 3) == 0 && (reinterpret_cast<uintptr_t>(confidence) & 3) == 0,
+                "ocv_depth_finalize_stats_fwd: misaligned output");
+  // (mirror: the flag of the TTA form for both outputs; a map that is not read may stay null)
+  FinStatsArgs a{pred, tta ? (pred_mirror ? pred_mirror : pmax_mirror) : nullptr, var, var_mirror, pmax, pmax_mirror, depth_std, confidence,
+                 h, w, H, W, B, H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f,
+                 max_depth - min_depth};
+  const long P = (long)H * W;
+  const bool vec = (P & 7) == 0 && (reinterpret_cast<uintptr_t>(depth_std) & 15) == 0 && (reinterpret_cast<uintptr_t>(confidence) & 15) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
+  if (vec && (W & 7) == 0 && !(h == H && w == W) && B <= 65535 && (long)tiles_x * tiles_y <= 0x7fffffffL) {
+    hipLaunchKernelGGL(depth_finalize_stats_tile_kernel, dim3(tiles_x * tiles_y, B), dim3(256), 0, st, a, tiles_x);
+  } else {
+    const long threads = vec ? P / 8 * B : P * B;
+    long grid = (threads + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    if (vec) hipLaunchKernelGGL(depth_finalize_stats_kernel<8>, dim3((int)grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(depth_finalize_stats_kernel<1>, dim3((int)grid), dim3(256), 0, st, a);
+  }
+  OCV_CHECK_LAUNCH("ocv_depth_finalize_stats_fwd");
   return 0;
 }

@@ -63,7 +63,8 @@ class GraphedGraphBins:
 
     def __init__(self, model, example_image: torch.Tensor, warmup: int = 2, eager_ops: Sequence[str] = (),
                  object_capacity: Optional[int] = None, object_group: Optional[int] = None, check_topology: bool = True,
-                 pairs: Optional[str] = None, in_flight: int = 1, stream: Optional["torch.cuda.Stream"] = None):
+                 pairs: Optional[str] = None, in_flight: int = 1, stream: Optional["torch.cuda.Stream"] = None,
+                 bin_stats: Optional[bool] = None):
         """``stream``: the stream to capture on and replay on (default: a new one).  Callers that keep several graphs in flight pass
         streams from ``hip_ops.independent_streams`` -- two slots whose streams share a hardware queue serialise.
         ``in_flight``: how many batches the caller keeps in flight on this GPU (one graph per slot): the capture forks side streams
@@ -74,16 +75,20 @@ class GraphedGraphBins:
         graph_topology.py).  Another shape is REPORTED (RuntimeWarning + ``hip_ops.ROUTE_REPORT["graph_topology"]``) when the process
         runs on at most four hardware queues -- there every shape tried replays at full speed (profiles/r05_graph_shapes.txt) -- and
         RAISES, before anything is replayed, on more than four: that is the configuration in which forked graphs replayed 3.5 - 6 ms
-        slower per step and one hipGraphLaunch crashed in round 4."""
+        slower per step and one hipGraphLaunch crashed in round 4.
+        ``bin_stats``: None = the model's ``bin_stats`` as it stands NOW -- the flag is read once, at capture; every replay (and
+        the bf16-pair re-capture) then returns ``depth_var`` / ``confidence`` or not as this graph was captured, whatever the model's
+        flag says later."""
         if example_image.device.type != "cuda":
             raise RuntimeError("graph capture needs a GPU tensor")
         if pairs not in (None, "bf16"):
             raise ValueError("pairs must be None (the model's own decision) or 'bf16'")
         self.model = model
         self.pairs = pairs
+        self.bin_stats = bool(getattr(model, "bin_stats", False) if bin_stats is None else bin_stats)
         self.in_flight = max(1, int(in_flight))
         self._ctor = dict(warmup=warmup, object_capacity=object_capacity, object_group=object_group, check_topology=check_topology,
-                          in_flight=self.in_flight)
+                          in_flight=self.in_flight, bin_stats=self.bin_stats)
         self._fallback: Optional["GraphedGraphBins"] = None
         # fp16 range guard (hip_ops.RangeGuard): the word every fp16-pair producer of THIS graph's launches ORs into; taken behind
         # every replay into ``last_flag`` (device), read by ``tripped`` / ``checked`` where the caller reads results
@@ -183,10 +188,17 @@ class GraphedGraphBins:
             end()
         torch.cuda.current_stream().wait_stream(self.stream)
         torch.cuda.synchronize()
+        self.feat, self.queries, self.centers, self.bin_edges, self.detections = parts
+        if self.bin_stats != bool(getattr(model, "bin_stats", False)):
+            # the warm-up forwards ran the head with the MODEL's flag: size this graph's head workspaces with its own before they freeze
+            with self._route(), hip_ops.workspace_scope(self.scratch), torch.cuda.stream(self.stream), torch.no_grad():
+                model.head(self.feat, self.queries, self.centers, stats=self.bin_stats)
+            torch.cuda.current_stream().wait_stream(self.stream)
+            torch.cuda.synchronize()
         self.range_guard.flag.zero_()                    # (the capture run's islands executed once: start clean)
         self.scratch.freeze()
-        self.feat, self.queries, self.centers, self.bin_edges, self.detections = parts
-        self.ReturnType = model.ReturnType
+        from .modules.AdaBins import return_type
+        self.ReturnType = return_type(model.ReturnType._fields[:3], self.bin_stats)
         self.islands = [s[0] for s in self.segments if isinstance(s, tuple)]
 
     @torch.no_grad()
@@ -236,9 +248,12 @@ class GraphedGraphBins:
                         seg[1]()
                 else:
                     seg.replay()
-            depth = self.model.head(self.feat, self.queries, self.centers)
+            depth = self.model.head(self.feat, self.queries, self.centers, stats=self.bin_stats)
         if self.pairs is None:
             self.last_flag = self.range_guard.take()     # one-thread launch: flag -> last_flag, flag = 0 (nobody waits for it here)
+        if self.bin_stats:
+            return self.ReturnType(depth_pred=depth[0], bin_edges=self.bin_edges, detections=self.detections, depth_var=depth[1],
+                                   confidence=depth[2])
         return self.ReturnType(depth_pred=depth, bin_edges=self.bin_edges, detections=self.detections)
 
     def _route(self):

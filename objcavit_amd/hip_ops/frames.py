@@ -116,12 +116,18 @@ def colormap_scale(vmin: float, vmax: float) -> float:
 def depth_finalize(pred: torch.Tensor, min_depth: float, max_depth: float, size: Tuple[int, int],
                    pred_mirror: Optional[torch.Tensor] = None, want: Tuple[str, ...] = ("depth",), u16_scale: float = 1000.0,
                    colormap: Optional[torch.Tensor] = None, vmin: Optional[float] = None, vmax: Optional[float] = None,
-                   out: Optional[dict] = None) -> dict:
+                   out: Optional[dict] = None, var: Optional[torch.Tensor] = None, pmax: Optional[torch.Tensor] = None,
+                   var_mirror: Optional[torch.Tensor] = None, pmax_mirror: Optional[torch.Tensor] = None) -> dict:
     """The model's depth_pred [B, 1, h, w] (+ ``pred_mirror``, the output for the mirrored image, still mirrored) -> the final map at
     ``size`` = (H, W): flip-TTA average of the clamped maps (or the clamped map), bilinear align_corners resize, nan -> min_depth,
     +-inf -> max_depth -- the map ``depth_metrics`` evaluates, materialised.  ``want``: any of "depth" (fp32 [B, 1, H, W]),
     "depth_u16" ([B, H, W] = min(65535, rint(depth * u16_scale))), "rgb8" ([B, H, W, 3] through ``colormap``, uint8 [256, 3] on the
-    device, over [vmin, vmax]; default the depth range).  ``out``: {name: tensor} to write into.  -> {name: tensor}."""
+    device, over [vmin, vmax]; default the depth range), and -- from the bin head's statistics ``var`` / ``pmax`` (``bin_head(...,
+    stats=True)``; with ``pred_mirror`` also ``var_mirror`` / ``pmax_mirror``, still mirrored) -- "depth_std" and "confidence" (fp32
+    [B, 1, H, W]): standard deviation and peak probability of the MIXTURE of the source distributions under the same bilinear (and
+    TTA) weights, m = sum w_t d_t on the unclamped maps, std = sqrt(sum w_t (var_t + (d_t - m)^2)), confidence = sum w_t pmax_t;
+    nan -> max_depth - min_depth / 0.  They come from a second launch (ocv_depth_finalize_stats_fwd); the first three outputs are
+    what they are without them.  ``out``: {name: tensor} to write into.  -> {name: tensor}."""
     lib = _lib.load()
     _req(pred, "pred")
     if pred.dim() != 4 or pred.shape[1] != 1:
@@ -131,9 +137,20 @@ def depth_finalize(pred: torch.Tensor, min_depth: float, max_depth: float, size:
         if pred_mirror.shape != pred.shape:
             raise ValueError("depth_finalize: pred_mirror must have pred's shape")
     want = tuple(want)
-    bad = set(want) - {"depth", "depth_u16", "rgb8"}
+    bad = set(want) - {"depth", "depth_u16", "rgb8", "depth_std", "confidence"}
     if bad or not want:
-        raise ValueError(f"depth_finalize: want must name some of 'depth', 'depth_u16', 'rgb8' (got {want})")
+        raise ValueError(f"depth_finalize: want must name some of 'depth', 'depth_u16', 'rgb8', 'depth_std', 'confidence' (got {want})")
+    for name, need, t, tm in (("depth_std", "var", var, var_mirror), ("confidence", "pmax", pmax, pmax_mirror)):
+        if name not in want:
+            continue
+        if t is None or (pred_mirror is not None and tm is None):
+            raise ValueError(f"depth_finalize: '{name}' needs {need}{' and ' + need + '_mirror' if pred_mirror is not None else ''} "
+                             "(hip_ops.bin_head(..., stats=True))")
+        for nm, x in ((need, t), (need + "_mirror", tm if pred_mirror is not None else None)):
+            if x is not None:
+                _req(x, nm)
+                if x.shape != pred.shape:
+                    raise ValueError(f"depth_finalize: {nm} must have pred's shape")
     B, _, h, w = (int(s) for s in pred.shape)
     H, W = int(size[0]), int(size[1])
     if H < 1 or W < 1:
@@ -154,6 +171,22 @@ def depth_finalize(pred: torch.Tensor, min_depth: float, max_depth: float, size:
             raise ValueError(f"depth_finalize: colormap must be [256, 3], got {tuple(colormap.shape)}")
         scale = colormap_scale(lo, float(max_depth) if vmax is None else float(vmax))
         res["rgb8"] = _out_slice(out.get("rgb8"), (B, H, W, 3), torch.uint8, pred.device, "depth_finalize")
+    if "depth_std" in want or "confidence" in want:
+        sd = _out_slice(out.get("depth_std"), (B, 1, H, W), torch.float32, pred.device, "depth_finalize") if "depth_std" in want else None
+        cf = _out_slice(out.get("confidence"), (B, 1, H, W), torch.float32, pred.device, "depth_finalize") if "confidence" in want else None
+        tta = pred_mirror is not None
+        with timed("depth_finalize_stats"):
+            check(lib.ocv_depth_finalize_stats_fwd(pred.data_ptr(), _ptr(pred_mirror), _ptr(var) if sd is not None else None,
+                                                   _ptr(var_mirror) if sd is not None and tta else None,
+                                                   _ptr(pmax) if cf is not None else None,
+                                                   _ptr(pmax_mirror) if cf is not None and tta else None, h, w, float(min_depth),
+                                                   float(max_depth), H, W, _ptr(sd), _ptr(cf), B, _stream()), "ocv_depth_finalize_stats_fwd")
+        if sd is not None:
+            res["depth_std"] = sd
+        if cf is not None:
+            res["confidence"] = cf
+    if not res.keys() - {"depth_std", "confidence"}:
+        return res
     with timed("depth_finalize"):
         check(lib.ocv_depth_finalize_fwd(pred.data_ptr(), _ptr(pred_mirror), h, w, float(min_depth), float(max_depth), H, W,
                                          _ptr(res.get("depth")), _ptr(res.get("depth_u16")), float(u16_scale), _ptr(res.get("rgb8")),

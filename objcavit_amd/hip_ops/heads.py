@@ -231,7 +231,7 @@ def pixel_dot(feat: torch.Tensor, queries: torch.Tensor) -> torch.Tensor:
 
 
 def bin_head(feat: torch.Tensor, queries: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor,
-             centers: torch.Tensor, exact: bool = False) -> torch.Tensor:
+             centers: torch.Tensor, exact: bool = False, stats: bool = False):
     """depth [B,1,h,w] = sum_k softmax_k(conv1x1(pixel_dot(feat, queries)))_k * centers_k, fused.
     feat NCHW-contiguous: exact fp32 MFMA.  feat channels_last: logits as a TWO-term fp16 split with a scaled low term (22-bit
     products at the error of an fp32 FMA chain, three MFMAs per block, all 256 bins per workgroup) formed on TWO LEVELS -- every bin
@@ -239,7 +239,9 @@ def bin_head(feat: torch.Tensor, queries: torch.Tensor, w_out: torch.Tensor, b_o
     e^-24 of a pixel's largest (csrc/bin_head.hip: OCV_BINHEAD=h2, the default; h2dense = every tile in full, round 4's kernel),
     as a THREE-term bf16 split (OCV_BINHEAD=split3: six MFMAs, two bin halves + a merge launch; fp32's RANGE -- also what a
     forward inside ``bf16_pairs()``, the range guard's fallback, takes), or on the exact fp32 MFMA kernel with ``exact=True`` /
-    OCV_BINHEAD=exact."""
+    OCV_BINHEAD=exact.
+    ``stats=True`` -> (depth, var, pmax), all [B,1,h,w]: the variance sum_k p_k (c_k - depth)^2 (m^2, >= 0) and the largest
+    probability of the same softmax, from the STATS instantiation of the same route's kernel (fp64 moments; depth keeps its bits)."""
     lib = _lib.load()
     mode = os.environ.get("OCV_BINHEAD", "h2")              # read per call
     if mode not in ("h2", "h2dense", "split3", "exact"):
@@ -265,8 +267,16 @@ def bin_head(feat: torch.Tensor, queries: torch.Tensor, w_out: torch.Tensor, b_o
     check(lib.ocv_bin_head_fold_fwd(queries.data_ptr(), queries.stride(0), queries.stride(1), w2.data_ptr(), wf.data_ptr(), B,
                                     Cc, Q, nbins, _stream()), "ocv_bin_head_fold_fwd")
     route = 0 if not cl else (1 if exact else ({"h2": 4, "h2dense": 3}.get(mode, 2)))          # include/objcavit_hip.h: ocv_bin_head_folded_fwd
-    npart = int(lib.ocv_bin_head_partials_bytes(B, h * w)) if route == 2 else 0
+    sizer = lib.ocv_bin_head_stats_partials_bytes if stats else lib.ocv_bin_head_partials_bytes
+    npart = int(sizer(B, h * w)) if route == 2 else 0
     part = workspace(npart, feat.device, "bin_head_partials") if npart else None
+    if stats:
+        var, pmax = torch.empty_like(depth), torch.empty_like(depth)
+        with timed("bin_head"):
+            check(lib.ocv_bin_head_folded_stats_fwd(feat.data_ptr(), route, wf.data_ptr(), b_out.data_ptr(), centers.data_ptr(),
+                                                    depth.data_ptr(), B, Cc, nbins, h * w, _ptr(part), npart, var.data_ptr(),
+                                                    pmax.data_ptr(), _stream()), "ocv_bin_head_folded_stats_fwd")
+        return depth, var, pmax
     with timed("bin_head"):          # the logit / softmax / depth launch(es): one, or the split-3 halves + merge
         check(lib.ocv_bin_head_folded_ws_fwd(feat.data_ptr(), route, wf.data_ptr(), b_out.data_ptr(),
                                              centers.data_ptr(), depth.data_ptr(), B, Cc, nbins, h * w, _ptr(part), npart,

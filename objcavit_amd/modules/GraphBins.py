@@ -20,7 +20,6 @@ from __future__ import annotations
 import logging
 import os
 import sys
-from collections import namedtuple
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -28,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip_ops
-from .AdaBins import bin_edges_and_centers
+from .AdaBins import BinStats, bin_edges_and_centers
 from .DenseFeatureExtractor import DenseFeatureExtractor
 from .ObjCAViT import ObjCAViT, PaddedObjects
 
@@ -88,17 +87,18 @@ def _record_on(result, stream) -> None:
             _record_on(t, stream)
 
 
-class GraphBins(nn.Module):
+class GraphBins(BinStats, nn.Module):
     images_are_independent = True      # an image's result does not depend on its batch mates (per object group: SURVEY.md Q3)
+    _base_fields = ('depth_pred', 'bin_edges', 'detections')
 
-    def __init__(self, args, object_provider: Optional[Callable] = None, backbone: nn.Module = None):
+    def __init__(self, args, object_provider: Optional[Callable] = None, backbone: nn.Module = None, bin_stats: bool = False):
         super().__init__()
         self.args = args
         self.logger = logging.getLogger(__name__)
         self._encoder_params_module_list = []
         self._non_encoder_params_module_list = []
         self._frozen_params_module_list = []
-        self.ReturnType = namedtuple('ReturnType', ['depth_pred', 'bin_edges', 'detections'])
+        self.bin_stats = bin_stats          # sets ReturnType: namedtuple('ReturnType', ['depth_pred', 'bin_edges', 'detections'])
 
         self.dense_feature_extractor = DenseFeatureExtractor(self.args, backbone=backbone)
         self._encoder_params_module_list.append(self.dense_feature_extractor.encoder)
@@ -184,10 +184,6 @@ class GraphBins(nn.Module):
         bin_edges, centers = bin_edges_and_centers(bin_widths_normed, ds.min_depth, ds.max_depth)
         return feat, queries, centers, bin_edges, detections
 
-    def head(self, feat, queries, centers):
-        conv = self.conv_out[0]
-        return hip_ops.bin_head(feat, queries, conv.weight.detach(), conv.bias.detach(), centers)
-
     def forward(self, image, object_features=None, object_xywh_list: Optional[List[Optional[torch.Tensor]]] = None,
                 pad_objects_to: Optional[int] = None, object_group: Optional[int] = None):
         """``pad_objects_to``: the longest object list of the GLOBAL batch when ``image`` is one rank's shard of it
@@ -196,6 +192,9 @@ class GraphBins(nn.Module):
         def run():
             feat, queries, centers, bin_edges, detections = self.forward_until_head(image, object_features, object_xywh_list,
                                                                                     pad_objects_to, object_group)
+            if self.bin_stats:
+                depth_pred, var, pmax = self.head(feat, queries, centers)
+                return self.ReturnType(depth_pred=depth_pred, bin_edges=bin_edges, detections=detections, depth_var=var, confidence=pmax)
             depth_pred = self.head(feat, queries, centers)
             return self.ReturnType(depth_pred=depth_pred, bin_edges=bin_edges, detections=detections)
 

@@ -26,9 +26,11 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
 IMAGENET_STD = (0.229, 0.224, 0.225)
 KB_CROP = (352, 1216)                          # modules/Preprocess.py:104-107
 _DEPTH_FACTOR = {"nyu": 1000.0, "kitti": 256.0}     # params/basicParams.yaml depth_norm_factor of the two dataset blocks
-WANT = ("depth", "depth_u16", "rgb8")
+WANT = ("depth", "depth_u16", "rgb8", "depth_std", "confidence")
+STATS_WANT = ("depth_std", "confidence")       # the outputs that need the model's ``bin_stats``
 
-PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "records", "bin_edges"])
+PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "records", "bin_edges", "depth_std", "confidence"],
+                           defaults=(None, None))
 
 Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
 
@@ -168,21 +170,49 @@ class _Ends:
         return out
 
     def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int, want: Tuple[str, ...],
-               edges) -> PredictResult:
-        """Final map + (with ground truth) the metric launch, on the current stream."""
+               edges, stats=None) -> PredictResult:
+        """Final map + (with ground truth) the metric launch, on the current stream.  ``stats``: (var, pmax, var_mirror, pmax_mirror)
+        of the same forward(s) when ``want`` names "depth_std" / "confidence"."""
         pred = out.contiguous()
         mirror = None if mirror is None else mirror.contiguous()
         maps = {}
         if want:
             cmap = self._on(pred.device, True)["cmap"] if "rgb8" in want else None
+            var, pmax, var_m, pmax_m = (None if t is None else t.contiguous() for t in (stats or (None,) * 4))
             maps = hip_ops.depth_finalize(pred, self.min_depth, self.max_depth, size, pred_mirror=mirror, want=want,
-                                          u16_scale=self.u16_scale, colormap=cmap, vmin=self.vmin, vmax=self.vmax)
+                                          u16_scale=self.u16_scale, colormap=cmap, vmin=self.vmin, vmax=self.vmax,
+                                          var=var, pmax=pmax, var_mirror=var_m, pmax_mirror=pmax_m)
         rec = None
         if depth_gt is not None:
             H, W = depth_gt.shape[2:]
             rec = _records(pred, mirror, edges, depth_gt, self.min_depth, self.max_depth, crop_box(self.args, H, W), first_image_id,
                            self.loss)
-        return PredictResult(maps.get("depth"), maps.get("depth_u16"), maps.get("rgb8"), rec, edges)
+        return PredictResult(maps.get("depth"), maps.get("depth_u16"), maps.get("rgb8"), rec, edges, maps.get("depth_std"),
+                             maps.get("confidence"))
+
+
+def _need_stats(want) -> bool:
+    return any(w in STATS_WANT for w in want)
+
+
+def _turn_stats_on(model) -> None:
+    """"depth_std" / "confidence" are wanted: the model must return ``depth_var`` / ``confidence``.  A module gets its ``bin_stats`` set;
+    a captured graph read the flag when it was captured and cannot change."""
+    from .graph import GraphedGraphBins
+    if isinstance(model, GraphedGraphBins):
+        if not model.bin_stats:
+            raise ValueError("want names 'depth_std' / 'confidence', but this graph was captured without bin_stats: set "
+                             "model.bin_stats = True before the capture (or pass GraphedGraphBins(..., bin_stats=True))")
+    elif not getattr(model, "bin_stats", False):
+        if not hasattr(type(model), "bin_stats"):
+            raise ValueError(f"want names 'depth_std' / 'confidence', but {type(model).__name__} has no bin_stats")
+        model.bin_stats = True
+
+
+def _stats_of(out, B: int, mirrored: bool):
+    """(var, pmax, var_mirror, pmax_mirror) of a joint [batch | mirrored batch] output (or of a plain one)."""
+    v, c = out.depth_var, out.confidence
+    return (v[:B], c[:B], v[B:], c[B:]) if mirrored else (v, c, None, None)
 
 
 def _check_want(want) -> Tuple[str, ...]:
@@ -201,7 +231,10 @@ class Predictor:
     [B, 1, H, W] metres, or the uint16 maps of the 16-bit PNGs (tensor or list; same crop, / depth_norm_factor).  ``want``: any of
     "depth" (fp32 [B, 1, H, W] at the cropped input size), "depth_u16" ([B, H, W], x ``u16_scale``: the dataset's PNG convention),
     "rgb8" ([B, H, W, 3] through ``colormap`` -- a uint8 [256, 3] tensor or a matplotlib name, default "inferno_r" -- over
-    [vmin, vmax], default the dataset's depth range).  ``records``: the [B, 10] / [B, 16] table of ``ValidationStep`` when ground
+    [vmin, vmax], default the dataset's depth range), "depth_std" / "confidence" (fp32 [B, 1, H, W]: standard deviation in metres and
+    largest bin probability of the predicted depth distribution -- the mixture of the source pixels' distributions under the same
+    TTA and bilinear weights; wanting either sets ``model.bin_stats = True``, a captured graph must have been captured with it).
+    ``records``: the [B, 10] / [B, 16] table of ``ValidationStep`` when ground
     truth is given; ``bin_edges``: those of the un-mirrored forward (a captured graph hands out its static tensor).
     ``model``: GraphBins / AdaBins, or a ``GraphedGraphBins`` captured for the [batch | mirrored batch] shape with
     ``object_group = B`` -- the frames are then ingested straight into its static input and it is called through ``checked``."""
@@ -217,7 +250,8 @@ class Predictor:
         return fn(*a) if fn is not None else self.model(*a)
 
     def _forward(self, frames: List[torch.Tensor], B: int):
-        """(output of the un-mirrored forward, mirrored forward's depth or None): ``ValidationStep._forward_pair`` fed by the ingest."""
+        """(output of the un-mirrored forward, the mirrored forward's output fields or None): ``ValidationStep._forward_pair`` fed by
+        the ingest.  The mirrored half keeps ``depth_pred`` and, with ``bin_stats``, ``depth_var`` / ``confidence``."""
         static = getattr(self.model, "static_image", None)
         if not self.flip_tta:
             fits = static is not None and int(static.shape[0]) == B and tuple(static.shape[2:]) == self.ends.window_of(frames)
@@ -229,20 +263,26 @@ class Predictor:
             first = self._call(both[:B])
             if static is not None:
                 first = type(first)(**{k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in first._asdict().items()})
-            return first, self._call(both[B:]).depth_pred
+            return first, self._call(both[B:])
         out = self.model(both, None, None, None, B) if _takes_group(self.model) else self._call(both)
         first = type(out)(**{k: (None if v is None else v[:B]) for k, v in out._asdict().items()})
-        return first, out.depth_pred[B:]
+        return first, type(out)(**{k: (None if v is None else v[B:]) for k, v in out._asdict().items()})
 
     @torch.no_grad()
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",)) -> PredictResult:
         want = _check_want(want)
+        if _need_stats(want):
+            _turn_stats_on(self.model)
         frames = _frame_list(frames_u8, "frames_u8", 4)
         B = sum(int(f.shape[0]) for f in frames)
         size = self.ends.window_of(frames)
         out, mirror = self._forward(frames, B)
         gt = self.ends.ground_truth(depth_gt, B)
-        return self.ends.finish(out.depth_pred, mirror, size, gt, first_image_id, want, getattr(out, "bin_edges", None))
+        stats = None
+        if _need_stats(want):
+            stats = (out.depth_var, out.confidence) + ((None, None) if mirror is None else (mirror.depth_var, mirror.confidence))
+        return self.ends.finish(out.depth_pred, None if mirror is None else mirror.depth_pred, size, gt, first_image_id, want,
+                                getattr(out, "bin_edges", None), stats)
 
 
 class PipelinedPredictor:
@@ -275,6 +315,8 @@ class PipelinedPredictor:
             hip_ops.ROUTE_REPORT["PipelinedPredictor"] = note
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
+        if _need_stats(self.want):
+            _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop)
         self.flip_tta = flip_tta
         ex = _frame_list(example_frames, "example_frames", 4)
@@ -294,8 +336,9 @@ class PipelinedPredictor:
         B = self.B
         edges = getattr(out, "bin_edges", None)
         edges = None if edges is None else edges[:B]
+        stats = _stats_of(out, B, self.flip_tta) if _need_stats(self.want) else None
         res = self.ends.finish(out.depth_pred[:B], out.depth_pred[B:] if self.flip_tta else None, self.size, gt, first_image_id,
-                               self.want, edges)
+                               self.want, edges, stats)
         return res._replace(bin_edges=edges.clone() if (self.want_edges and edges is not None) else None)
 
     @torch.no_grad()
