@@ -8,7 +8,8 @@ bilinear align_corners resize to the input size, nan / inf fix (GraphBinsLM.py:1
 out in one more launch as fp32 metres, as the datasets' 16-bit PNG values and as a colour-mapped picture (csrc/depth_finalize.hip).
 With ground truth the existing metric launch adds the per-image records of a validation step.  ``flip_tta=False`` is the
 reference's own predict step, which uses no test-time augmentation (GraphBinsLM.py:295-301).  ``PipelinedPredictor`` keeps several
-such steps in flight on captured graphs, as ``PipelinedValidation`` does.
+such steps in flight on captured graphs: it and ``PipelinedValidation`` are the two subclasses of ``validation._SlotPipeline``, which
+owns the slots, their streams and the range-guard handling; the pair forward is ``validation._forward_pair`` for both steps.
 """
 from __future__ import annotations
 
@@ -19,8 +20,7 @@ import torch
 
 from . import hip_ops
 from ._lib import HipLibraryError
-from .dp import LOSS_FIELDS, RECORD_FIELDS
-from .validation import _joint_fits, _records, _takes_group, crop_box, hw_queue_note
+from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -103,8 +103,7 @@ class _Ends:
 
     def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
-        ds = _dataset(args)
-        self.min_depth, self.max_depth = float(ds.min_depth), float(ds.max_depth)
+        self.min_depth, self.max_depth = _depth_range(args)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -169,24 +168,24 @@ class _Ends:
             i += int(m.shape[0])
         return out
 
-    def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int, want: Tuple[str, ...],
-               edges, stats=None) -> PredictResult:
-        """Final map + (with ground truth) the metric launch, on the current stream.  ``stats``: (var, pmax, var_mirror, pmax_mirror)
-        of the same forward(s) when ``want`` names "depth_std" / "confidence"."""
-        pred = out.contiguous()
-        mirror = None if mirror is None else mirror.contiguous()
+    def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int,
+               want: Tuple[str, ...]) -> PredictResult:
+        """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
+        the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence"."""
+        pred = out.depth_pred.contiguous()
+        mirror_pred = None if mirror is None else mirror.depth_pred.contiguous()
+        edges = getattr(out, "bin_edges", None)
         maps = {}
         if want:
             cmap = self._on(pred.device, True)["cmap"] if "rgb8" in want else None
-            var, pmax, var_m, pmax_m = (None if t is None else t.contiguous() for t in (stats or (None,) * 4))
-            maps = hip_ops.depth_finalize(pred, self.min_depth, self.max_depth, size, pred_mirror=mirror, want=want,
+            stats = [getattr(o, k, None) if _need_stats(want) else None for o in (out, mirror) for k in ("depth_var", "confidence")]
+            stats = [None if t is None else t.contiguous() for t in stats]
+            maps = hip_ops.depth_finalize(pred, self.min_depth, self.max_depth, size, pred_mirror=mirror_pred, want=want,
                                           u16_scale=self.u16_scale, colormap=cmap, vmin=self.vmin, vmax=self.vmax,
-                                          var=var, pmax=pmax, var_mirror=var_m, pmax_mirror=pmax_m)
+                                          var=stats[0], pmax=stats[1], var_mirror=stats[2], pmax_mirror=stats[3])
         rec = None
         if depth_gt is not None:
-            H, W = depth_gt.shape[2:]
-            rec = _records(pred, mirror, edges, depth_gt, self.min_depth, self.max_depth, crop_box(self.args, H, W), first_image_id,
-                           self.loss)
+            rec = _records(pred, mirror_pred, edges, depth_gt, self.args, self.min_depth, self.max_depth, first_image_id, self.loss)
         return PredictResult(maps.get("depth"), maps.get("depth_u16"), maps.get("rgb8"), rec, edges, maps.get("depth_std"),
                              maps.get("confidence"))
 
@@ -207,12 +206,6 @@ def _turn_stats_on(model) -> None:
         if not hasattr(type(model), "bin_stats"):
             raise ValueError(f"want names 'depth_std' / 'confidence', but {type(model).__name__} has no bin_stats")
         model.bin_stats = True
-
-
-def _stats_of(out, B: int, mirrored: bool):
-    """(var, pmax, var_mirror, pmax_mirror) of a joint [batch | mirrored batch] output (or of a plain one)."""
-    v, c = out.depth_var, out.confidence
-    return (v[:B], c[:B], v[B:], c[B:]) if mirrored else (v, c, None, None)
 
 
 def _check_want(want) -> Tuple[str, ...]:
@@ -245,28 +238,14 @@ class Predictor:
         self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop)
         self.flip_tta = flip_tta
 
-    def _call(self, *a):
-        fn = getattr(self.model, "checked", None)
-        return fn(*a) if fn is not None else self.model(*a)
-
     def _forward(self, frames: List[torch.Tensor], B: int):
-        """(output of the un-mirrored forward, the mirrored forward's output fields or None): ``ValidationStep._forward_pair`` fed by
-        the ingest.  The mirrored half keeps ``depth_pred`` and, with ``bin_stats``, ``depth_var`` / ``confidence``."""
+        """(output of the un-mirrored forward, the mirrored forward's output or None): ``validation._forward_pair`` fed by the ingest,
+        which writes straight into a captured graph's static input when that has the step's shape."""
         static = getattr(self.model, "static_image", None)
+        fits = static is not None and tuple(static.shape[2:]) == self.ends.window_of(frames)
         if not self.flip_tta:
-            fits = static is not None and int(static.shape[0]) == B and tuple(static.shape[2:]) == self.ends.window_of(frames)
-            return self._call(self.ends.ingest(frames, out=static if fits else None)), None
-        joint = getattr(self.model, "images_are_independent", False) and _joint_fits(self.model, B)
-        fits = joint and static is not None and tuple(static.shape[2:]) == self.ends.window_of(frames)
-        both = self.ends.ingest(frames, out=static if fits else None)
-        if not joint:
-            first = self._call(both[:B])
-            if static is not None:
-                first = type(first)(**{k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in first._asdict().items()})
-            return first, self._call(both[B:])
-        out = self.model(both, None, None, None, B) if _takes_group(self.model) else self._call(both)
-        first = type(out)(**{k: (None if v is None else v[:B]) for k, v in out._asdict().items()})
-        return first, type(out)(**{k: (None if v is None else v[B:]) for k, v in out._asdict().items()})
+            return _call(self.model, self.ends.ingest(frames, out=static if fits and int(static.shape[0]) == B else None)), None
+        return _forward_pair(self.model, both=self.ends.ingest(frames, out=static if fits and _joint(self.model, B) else None))
 
     @torch.no_grad()
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",)) -> PredictResult:
@@ -277,21 +256,16 @@ class Predictor:
         B = sum(int(f.shape[0]) for f in frames)
         size = self.ends.window_of(frames)
         out, mirror = self._forward(frames, B)
-        gt = self.ends.ground_truth(depth_gt, B)
-        stats = None
-        if _need_stats(want):
-            stats = (out.depth_var, out.confidence) + ((None, None) if mirror is None else (mirror.depth_var, mirror.confidence))
-        return self.ends.finish(out.depth_pred, None if mirror is None else mirror.depth_pred, size, gt, first_image_id, want,
-                                getattr(out, "bin_edges", None), stats)
+        return self.ends.finish(out, mirror, size, self.ends.ground_truth(depth_gt, B), first_image_id, want)
 
 
-class PipelinedPredictor:
-    """``slots`` predict steps IN FLIGHT, modelled on ``PipelinedValidation``: one captured graph of the joint [batch | mirrored batch]
-    forward per slot, each on a stream with a hardware queue of its own (``hip_ops.independent_streams``).  ``submit`` ingests the
+class PipelinedPredictor(_SlotPipeline):
+    """``slots`` predict steps IN FLIGHT, on ``PipelinedValidation``'s slot pipeline (``validation._SlotPipeline``): one captured graph of
+    the joint [batch | mirrored batch] forward per slot, each on a stream with a hardware queue of its own.  ``submit`` ingests the
     frames DIRECTLY into the slot's static input -- no ``flip``, no ``cat``, no ``copy_`` of the image: the graph sees its own
     pointer and skips its copy --, replays, and writes the final map (and, with ground truth, the metric records) on the slot's
-    stream; ``collect`` returns the ``PredictResult`` of every submitted step in submission order, reads the steps' fp16 range-guard
-    words in one host copy and re-runs a tripped step from its kept frames on the bf16-pair capture.  ``bin_edges`` of a result is
+    stream; ``collect`` returns the ``PredictResult`` of every submitted step in submission order; a step whose fp16 range guard
+    tripped is ingested again from its kept frames for the re-run.  ``bin_edges`` of a result is
     None unless ``want`` names "bin_edges" (the graph's static tensor is then copied per step).  Wants ``GPU_MAX_HW_QUEUES`` >= slots
     set before the HIP runtime starts, like ``PipelinedValidation``.
 
@@ -301,18 +275,13 @@ class PipelinedPredictor:
         results = pp.collect()
     """
 
+    name = "PipelinedPredictor"
+
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
                  crop: Optional[Tuple[int, int, int, int]] = None):
-        from .graph import GraphedGraphBins
-        if slots < 1:
-            raise ValueError("PipelinedPredictor: slots must be >= 1")
-        note = hw_queue_note(slots)
-        if note:
-            import warnings
-            warnings.warn(f"PipelinedPredictor: {note}", RuntimeWarning, stacklevel=2)
-            hip_ops.ROUTE_REPORT["PipelinedPredictor"] = note
+        super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
         if _need_stats(self.want):
@@ -325,68 +294,33 @@ class PipelinedPredictor:
         both = self.ends.ingest(ex)
         if "rgb8" in self.want:
             self.ends._on(both.device, True)                 # the colour table is uploaded here, not inside a step
-        streams = hip_ops.independent_streams(slots, both.device) if slots > 1 else [None]
-        self.graphs = [GraphedGraphBins(model, both, object_capacity=object_capacity, object_group=self.B if flip_tta else None,
-                                        in_flight=slots, stream=streams[k]) for k in range(slots)]
-        self._next = 0
-        self._pending = []
-        self.rerun_steps = 0                                 # steps re-run on bf16 pairs by collect() (fp16 range guard)
+        self._capture(model, both, object_capacity, self.B if flip_tta else None)
 
-    def _finish(self, out, gt, first_image_id: int) -> PredictResult:
-        B = self.B
-        edges = getattr(out, "bin_edges", None)
-        edges = None if edges is None else edges[:B]
-        stats = _stats_of(out, B, self.flip_tta) if _need_stats(self.want) else None
-        res = self.ends.finish(out.depth_pred[:B], out.depth_pred[B:] if self.flip_tta else None, self.size, gt, first_image_id,
-                               self.want, edges, stats)
-        return res._replace(bin_edges=edges.clone() if (self.want_edges and edges is not None) else None)
+    def _stage(self, frames: List[torch.Tensor], g):
+        return self.ends.ingest(frames, out=g.static_image), frames
 
-    @torch.no_grad()
+    def _restage(self, frames: List[torch.Tensor]) -> torch.Tensor:
+        return self.ends.ingest(frames)                      # the slot's static input has long been overwritten: ingest again
+
+    def _finish(self, out, depth_gt, first_image_id: int) -> PredictResult:
+        gt = self.ends.ground_truth(depth_gt, self.B)
+        out, mirror = _split(out, self.B) if self.flip_tta else (out, None)
+        res = self.ends.finish(out, mirror, self.size, gt, first_image_id, self.want)
+        return res._replace(bin_edges=res.bin_edges.clone() if (self.want_edges and res.bin_edges is not None) else None)
+
+    def collect(self) -> List[PredictResult]:
+        """Wait for every submitted step; -> their results in submission order (and forget them)."""
+        return self._collect()
+
     def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None) -> None:
         """Enqueue one predict step on the next slot's stream; returns at once."""
         frames = _frame_list(frames_u8, "frames_u8", 4)
         if sum(int(f.shape[0]) for f in frames) != self.B or self.ends.window_of(frames) != self.size:
             raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")
-        g = self.graphs[self._next]
-        self._next = (self._next + 1) % len(self.graphs)
-        caller = torch.cuda.current_stream(frames[0].device)
-        g.stream.wait_stream(caller)                         # the frames / ground truth were produced on the caller's stream
-        with torch.cuda.stream(g.stream):
-            self.ends.ingest(frames, out=g.static_image)
-            out = g(g.static_image, object_features, object_xywh_list) if g.objects is not None else g(g.static_image)
-            gt = self.ends.ground_truth(depth_gt, self.B)
-            res = self._finish(out, gt, first_image_id)
         held = list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
-        for t in held:
-            t.record_stream(g.stream)                        # the caching allocator must not recycle them under the slot's launches
-        # frames and ground truth stay referenced until collect(): a step whose range guard tripped is re-run from them
-        self._pending.append((res, g.stream, g.last_flag, g, (frames, depth_gt, first_image_id, object_features, object_xywh_list)))
-
-    @torch.no_grad()
-    def collect(self) -> List[PredictResult]:
-        """Wait for every submitted step; -> their results in submission order (and forget them)."""
-        if not self._pending:
-            return []
-        for p in self._pending:
-            p[1].synchronize()
-        results = [p[0] for p in self._pending]
-        flags = [p[2] for p in self._pending]
-        if any(f is not None for f in flags):
-            dev = self._pending[0][3].static_image.device
-            hit = torch.cat([f if f is not None else torch.zeros(1, dtype=torch.int32, device=dev) for f in flags]).cpu()
-            for i in hit.nonzero().flatten().tolist():
-                _, _, _, g, (frames, depth_gt, first_id, of, ox) = self._pending[i]
-                both = self.ends.ingest(frames)              # the slot's static input has long been overwritten: ingest again
-                out = g.rerun_on_bf16(both, of, ox) if g.objects is not None else g.rerun_on_bf16(both)
-                results[i] = self._finish(out, self.ends.ground_truth(depth_gt, self.B), first_id)
-                self.rerun_steps += 1
-            torch.cuda.current_stream(dev).synchronize()
-        self._pending = []
-        return results
+        self._submit(frames, held, depth_gt, first_image_id, (object_features, object_xywh_list))
 
     def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
         """The record table [N * B, 10] ([N * B, 16] with ``loss``) of collected results that carried ground truth."""
         recs = [r.records for r in results if r.records is not None]
-        if not recs:
-            return torch.empty(0, len(RECORD_FIELDS) + (len(LOSS_FIELDS) if self.ends.loss else 0))
-        return torch.cat(recs, 0)
+        return torch.cat(recs, 0) if recs else _empty_records(self.ends.loss)

@@ -12,7 +12,8 @@ running-average numbers, ``totals`` below its pixel-total numbers.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from collections import namedtuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -32,6 +33,55 @@ def crop_box(args, H: int, W: int) -> Optional[Tuple[int, int, int, int]]:
     return None
 
 
+def _depth_range(args) -> Tuple[float, float]:
+    """(min_depth, max_depth) of ``args.basic.dataset``."""
+    ds = args[args.basic.dataset]
+    return float(ds.min_depth), float(ds.max_depth)
+
+
+def _empty_records(loss: bool) -> torch.Tensor:
+    """The record table of no step at all: [0, 10], or [0, 16] with the loss pieces, on the host."""
+    return torch.empty(0, len(RECORD_FIELDS) + (len(LOSS_FIELDS) if loss else 0))
+
+
+def _call(model, *a):
+    """One forward.  A captured graph is called through ``checked``: its fp16 range guard is read here (a sequential step
+    reads its result next anyway) and a tripped batch re-run on the bf16-pair capture; an eager model guards itself."""
+    fn = getattr(model, "checked", None)
+    return fn(*a) if fn is not None else model(*a)
+
+
+def _joint(model, B: int, allowed: bool = True) -> bool:
+    """Whether image and mirror go through ``model`` as ONE forward over the 2B images [batch | mirrored batch]."""
+    return bool(allowed and getattr(model, "images_are_independent", False) and _joint_fits(model, B))
+
+
+def _split(out, B: int):
+    """(un-mirrored half, mirrored half) of the output of a joint forward over [batch | mirrored batch]: views, no launch."""
+    return tuple(type(out)(**{k: (None if v is None else v[s]) for k, v in out._asdict().items()}) for s in (slice(0, B), slice(B, None)))
+
+
+def _forward_pair(model, halves=None, both=None, joint: bool = True):
+    """(output of the un-mirrored forward, output of the mirrored forward -- still mirrored) of ``halves`` = (batch, mirrored batch)
+    or of ``both`` = the 2B tensor [batch | mirrored batch], whichever the caller has: the other form is made here only on the route
+    that needs it (``cat`` for the joint forward, two slices for two calls)."""
+    assert (halves is None) != (both is None), "_forward_pair takes the two halves or the 2B tensor, not both and not neither"
+    B = int(halves[0].shape[0]) if both is None else int(both.shape[0]) // 2
+    if not _joint(model, B, joint):
+        image, mirrored = (both[:B], both[B:]) if halves is None else halves
+        first = _call(model, image)
+        if getattr(model, "static_image", None) is not None:
+            # a captured graph hands out its STATIC result tensors (bin_edges): the mirror's replay would overwrite them
+            first = type(first)(**{k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in first._asdict().items()})
+        return first, _call(model, mirrored)
+    if both is None:
+        both = torch.cat(halves, dim=0)
+    # the provider sees the mirrored images as images of their own, exactly as the reference's detector does (:173); the two
+    # halves keep their own Nmax (object_group = B): bit for bit what two calls compute, up to batch-size-dependent kernel
+    # dispatch (split-K, tile shapes)
+    return _split(model(both, None, None, None, B) if _takes_group(model) else _call(model, both), B)
+
+
 class ValidationStep:
     """``joint`` (default): image and mirror as one 2B-image forward when the model declares ``images_are_independent`` (GraphBins,
     AdaBins, a GraphedGraphBins captured for 2B images with ``object_group = B``); False: two forwards, as the reference issues
@@ -39,32 +89,15 @@ class ValidationStep:
 
     def __init__(self, model, args, flip_tta: bool = True, joint: bool = True, loss: bool = False):
         self.model, self.args, self.flip_tta, self.joint, self.loss = model, args, flip_tta, joint, loss
-        ds = args[args.basic.dataset]
-        self.min_depth, self.max_depth = float(ds.min_depth), float(ds.max_depth)
+        self.min_depth, self.max_depth = _depth_range(args)
 
     def _call(self, *a):
-        """One forward.  A captured graph is called through ``checked``: its fp16 range guard is read here (this sequential step
-        reads its result next anyway) and a tripped batch re-run on the bf16-pair capture; an eager model guards itself."""
-        fn = getattr(self.model, "checked", None)
-        return fn(*a) if fn is not None else self.model(*a)
+        return _call(self.model, *a)
 
     def _forward_pair(self, image: torch.Tensor):
         """(output of the un-mirrored forward, depth of the mirrored forward -- still mirrored, as the metric kernel wants it)."""
-        B = image.shape[0]
-        mirrored = image.flip(dims=[3])
-        if not (self.joint and getattr(self.model, "images_are_independent", False) and _joint_fits(self.model, B)):
-            first = self._call(image)
-            if getattr(self.model, "static_image", None) is not None:
-                # a captured graph hands out its STATIC result tensors (bin_edges): the mirror's replay would overwrite them
-                first = type(first)(**{k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in first._asdict().items()})
-            return first, self._call(mirrored).depth_pred
-        both = torch.cat([image, mirrored], dim=0)
-        # the provider sees the mirrored images as images of their own, exactly as the reference's detector does (:173); the two
-        # halves keep their own Nmax (object_group = B): bit for bit what two calls compute, up to batch-size-dependent kernel
-        # dispatch (split-K, tile shapes)
-        out = self.model(both, None, None, None, B) if _takes_group(self.model) else self._call(both)
-        first = type(out)(**{k: (None if v is None else v[:B]) for k, v in out._asdict().items()})
-        return first, out.depth_pred[B:]
+        out, mirror = _forward_pair(self.model, halves=(image, image.flip(dims=[3])), joint=self.joint)
+        return out, mirror.depth_pred
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, depth_gt: torch.Tensor, first_image_id: int = 0):
@@ -75,14 +108,14 @@ class ValidationStep:
             out, mirror = self._forward_pair(image)
         else:
             out, mirror = self._call(image), None
-        H, W = depth_gt.shape[2:]
-        return _records(out.depth_pred, mirror, getattr(out, "bin_edges", None), depth_gt, self.min_depth, self.max_depth,
-                        crop_box(self.args, H, W), first_image_id, self.loss), out
+        return _records(out.depth_pred, mirror, getattr(out, "bin_edges", None), depth_gt, self.args, self.min_depth, self.max_depth,
+                        first_image_id, self.loss), out
 
 
-def _records(pred, mirror, bin_edges, depth_gt, min_depth, max_depth, box, first_image_id, loss) -> torch.Tensor:
+def _records(pred, mirror, bin_edges, depth_gt, args, min_depth, max_depth, first_image_id, loss) -> torch.Tensor:
     """The metric launch of a validation step: [B, 10], or [B, 16] with the loss pieces."""
     mirror = None if mirror is None else mirror.contiguous()
+    box = crop_box(args, *depth_gt.shape[2:])
     if not loss:
         return hip_ops.depth_metrics(pred.contiguous(), depth_gt.contiguous(), min_depth, max_depth, crop=box, pred_mirror=mirror,
                                      first_image_id=first_image_id)
@@ -133,7 +166,86 @@ def hw_queue_note(slots: int) -> Optional[str]:
             "share a hardware queue serialise (measured 781 vs 840 img/s)")
 
 
-class PipelinedValidation:
+_Pending = namedtuple("_Pending", ["result", "graph", "flag", "kept", "depth_gt", "first_image_id", "objects"])
+
+
+class _SlotPipeline:
+    """``slots`` steps IN FLIGHT -- what ``PipelinedValidation`` and ``PipelinedPredictor`` share: one captured graph per slot, each on
+    a stream with a hardware queue of its own, the steps dealt to the slots round-robin, and at ``collect()`` the fp16 range guard:
+    every step's guard word (``g.last_flag``) read in ONE host copy, a tripped step re-run on its slot's bf16-pair capture (captured
+    once, on the first trip) from the inputs kept since ``submit()``.  A subclass supplies ``_stage`` (inputs -> the graph's input and
+    what a re-run is made from, on the slot's stream), ``_finish`` (graph output -> the step's result) and, where a re-run's input has
+    to be made again, ``_restage``."""
+
+    name = None                                              # the subclass's public name: in its messages and its ROUTE_REPORT key
+
+    def __init__(self, slots: int):
+        name = self.name
+        if slots < 1:
+            raise ValueError(f"{name}: slots must be >= 1")
+        note = hw_queue_note(slots)
+        if note:
+            import warnings
+            warnings.warn(f"{name}: {note}", RuntimeWarning, stacklevel=3)
+            hip_ops.ROUTE_REPORT[name] = note
+        self._slots = slots
+        self._next = 0
+        self._pending: List[_Pending] = []
+        self.rerun_steps = 0                                 # steps re-run on bf16 pairs by collect() (fp16 range guard)
+
+    def _capture(self, model, example: torch.Tensor, object_capacity: Optional[int], object_group: Optional[int]) -> None:
+        """One graph of ``example`` ([batch | mirrored batch] with ``object_group`` = the batch, or the batch alone) per slot."""
+        from .graph import GraphedGraphBins
+        # slot streams that do NOT share a hardware queue (checked: hip_ops.independent_streams; the runtime's own dealing put two of
+        # four consecutive streams on one queue -- 349 instead of 441 validated img/s at bs 1, profiles/r06_stream_queues.txt)
+        streams = hip_ops.independent_streams(self._slots, example.device) if self._slots > 1 else [None]
+        self.graphs = [GraphedGraphBins(model, example, object_capacity=object_capacity, object_group=object_group,
+                                        in_flight=self._slots, stream=s) for s in streams]
+
+    @staticmethod
+    def _replay(g, staged: torch.Tensor, objects, rerun: bool = False):
+        """A graph with live objects takes the caller's (None: it asks the model's provider); one with baked-in objects takes none."""
+        fn = g.rerun_on_bf16 if rerun else g
+        return fn(staged, *objects) if g.objects is not None else fn(staged)
+
+    def _restage(self, kept):
+        return kept
+
+    @torch.no_grad()
+    def _submit(self, inputs, held, depth_gt, first_image_id: int, objects) -> None:
+        """``held``: the caller's tensors that the step reads."""
+        g = self.graphs[self._next]
+        self._next = (self._next + 1) % len(self.graphs)
+        g.stream.wait_stream(torch.cuda.current_stream(held[0].device))     # the inputs were produced on the caller's stream
+        with torch.cuda.stream(g.stream):
+            staged, kept = self._stage(inputs, g)
+            result = self._finish(self._replay(g, staged, objects), depth_gt, first_image_id)
+        for t in held:
+            t.record_stream(g.stream)                        # the caching allocator must not recycle them under the slot's launches
+        # the step's inputs stay referenced until collect(): a tripped step is re-run from them
+        self._pending.append(_Pending(result, g, g.last_flag, kept, depth_gt, first_image_id, objects))
+
+    @torch.no_grad()
+    def _collect(self) -> list:
+        pending = self._pending
+        for p in pending:
+            p.graph.stream.synchronize()
+        results = [p.result for p in pending]
+        flags = [p.flag for p in pending if p.flag is not None]
+        if flags:
+            dev = flags[0].device
+            hit = torch.cat([torch.zeros(1, dtype=torch.int32, device=dev) if p.flag is None else p.flag for p in pending]).cpu()
+            for i in hit.nonzero().flatten().tolist():
+                p = pending[i]
+                out = self._replay(p.graph, self._restage(p.kept), p.objects, rerun=True)
+                results[i] = self._finish(out, p.depth_gt, p.first_image_id)
+                self.rerun_steps += 1
+            torch.cuda.current_stream(dev).synchronize()
+        self._pending = []
+        return results
+
+
+class PipelinedValidation(_SlotPipeline):
     """The reference's validation loop -- one image at a time (main.py:58), model(image) and model(mirror) per image
     (modules/GraphBinsLM.py:159,173) -- with ``slots`` validation steps IN FLIGHT: each slot is a hipGraph of the joint
     [batch | mirrored batch] forward captured on a stream of its own (objcavit_amd/graph.py; live objects with
@@ -155,82 +267,40 @@ class PipelinedValidation:
         records = pv.collect()                                # [N, 10] per-image records, submission order
     """
 
+    name = "PipelinedValidation"
+
     def __init__(self, model, args, example_image: torch.Tensor, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False):
-        from .graph import GraphedGraphBins
-        if slots < 1:
-            raise ValueError("PipelinedValidation: slots must be >= 1")
-        note = hw_queue_note(slots)
-        if note:
-            import warnings
-            warnings.warn(f"PipelinedValidation: {note}", RuntimeWarning, stacklevel=2)
-            hip_ops.ROUTE_REPORT["PipelinedValidation"] = note
+        super().__init__(slots)
         self.args, self.flip_tta, self.loss = args, flip_tta, loss
-        ds = args[args.basic.dataset]
-        self.min_depth, self.max_depth = float(ds.min_depth), float(ds.max_depth)
+        self.min_depth, self.max_depth = _depth_range(args)
         self.B = int(example_image.shape[0])
-        both = torch.cat([example_image, example_image.flip(dims=[3])], 0) if flip_tta else example_image
-        # slot streams that do NOT share a hardware queue (checked: hip_ops.independent_streams; the runtime's own dealing put two of
-        # four consecutive streams on one queue -- 349 instead of 441 validated img/s at bs 1, profiles/r06_stream_queues.txt)
-        streams = hip_ops.independent_streams(slots, example_image.device) if slots > 1 else [None]
-        self.graphs = [GraphedGraphBins(model, both, object_capacity=object_capacity, object_group=self.B if flip_tta else None,
-                                        in_flight=slots, stream=streams[k]) for k in range(slots)]
-        self._next = 0
-        self._pending = []
-        self.rerun_steps = 0                                 # steps re-run on bf16 pairs by collect() (fp16 range guard)
+        self._capture(model, self._stage(example_image)[0], object_capacity, self.B if flip_tta else None)
 
-    @torch.no_grad()
     def submit(self, image: torch.Tensor, depth_gt: torch.Tensor, first_image_id: int = 0, object_features=None, object_xywh_list=None) -> None:
         """Enqueue one validation step (image [B, 3, H, W] as captured, ground truth [B, 1, H', W']) on the next slot's stream;
         returns at once.  ``object_features`` / ``object_xywh_list``: the objects of the 2B images [batch | mirrored batch] for a
         graph with ``object_capacity`` (default: the model's provider is asked, on the slot's stream)."""
         if tuple(image.shape[1:]) != tuple(self.graphs[0].static_image.shape[1:]) or image.shape[0] != self.B:
             raise ValueError(f"captured for images {(self.B,) + tuple(self.graphs[0].static_image.shape[1:])}, got {tuple(image.shape)}")
-        g = self.graphs[self._next]
-        self._next = (self._next + 1) % len(self.graphs)
-        caller = torch.cuda.current_stream(image.device)
-        g.stream.wait_stream(caller)                         # image / ground truth were produced on the caller's stream
-        with torch.cuda.stream(g.stream):
-            both = torch.cat([image, image.flip(dims=[3])], 0) if self.flip_tta else image
-            out = g(both, object_features, object_xywh_list) if g.objects is not None else g(both)
-            rec = self._records(out, depth_gt, first_image_id)
-        for t in (image, depth_gt):
-            t.record_stream(g.stream)                        # the caching allocator must not recycle them under the slot's launches
-        # the step's inputs stay referenced until collect(): a step whose fp16 range guard tripped (``g.last_flag``, read there in ONE
-        # host copy for all pending steps) is re-run from them on the bf16-pair capture
-        self._pending.append((rec, g.stream, g.last_flag, g, (both, depth_gt, first_image_id, object_features, object_xywh_list)))
+        self._submit(image, [image, depth_gt], depth_gt, first_image_id, (object_features, object_xywh_list))
 
-    def _records(self, out, depth_gt: torch.Tensor, first_image_id: int) -> torch.Tensor:
-        H, W = depth_gt.shape[2:]
-        B = self.B
+    def _stage(self, image: torch.Tensor, g=None):
+        both = torch.cat([image, image.flip(dims=[3])], 0) if self.flip_tta else image
+        return both, both
+
+    def _finish(self, out, depth_gt: torch.Tensor, first_image_id: int) -> torch.Tensor:
         # (with ``loss``: the graph's STATIC bin_edges, un-mirrored half, read by this launch on the slot's stream before the slot's
         # next replay can overwrite them)
-        edges = getattr(out, "bin_edges", None)
+        B, edges = self.B, getattr(out, "bin_edges", None)
         return _records(out.depth_pred[:B], out.depth_pred[B:] if self.flip_tta else None, None if edges is None else edges[:B],
-                        depth_gt, self.min_depth, self.max_depth, crop_box(self.args, H, W), first_image_id, self.loss)
+                        depth_gt, self.args, self.min_depth, self.max_depth, first_image_id, self.loss)
 
     def collect(self) -> torch.Tensor:
         """Wait for every submitted step; -> records [N * B, 10] ([N * B, 16] with ``loss``) in submission order (and forget them).  The steps' inputs are held
         until here (fp16 range guard: a tripped step is re-run on bf16 pairs): call it every few hundred steps on a long run."""
-        if not self._pending:
-            return torch.empty(0, len(RECORD_FIELDS) + (len(LOSS_FIELDS) if self.loss else 0))
-        for p in self._pending:
-            p[1].synchronize()
-        recs = [p[0] for p in self._pending]
-        flags = [p[2] for p in self._pending]
-        if any(f is not None for f in flags):
-            # fp16 range guard: one host read for all pending steps; a tripped step is re-run on its slot's bf16-pair capture
-            # (captured once, on the first trip) from the inputs kept since submit()
-            hit = torch.cat([f if f is not None else torch.zeros(1, dtype=torch.int32, device=recs[0].device) for f in flags]).cpu()
-            for i in hit.nonzero().flatten().tolist():
-                _, _, _, g, (both, depth_gt, first_id, of, ox) = self._pending[i]
-                out = g.rerun_on_bf16(both, of, ox) if g.objects is not None else g.rerun_on_bf16(both)
-                recs[i] = self._records(out, depth_gt, first_id)
-                self.rerun_steps += 1
-            torch.cuda.current_stream(recs[0].device).synchronize()
-        out = torch.cat(recs, 0)
-        self._pending = []
-        return out
+        recs = self._collect()
+        return torch.cat(recs, 0) if recs else _empty_records(self.loss)
 
 
 def totals(records: torch.Tensor) -> Dict[str, float]:

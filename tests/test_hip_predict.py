@@ -414,3 +414,136 @@ def test_pipelined_predictor_reruns_a_tripped_step_at_collect(ops):
     seq = Predictor(m, args, flip_tta=False)                                  # eager: the model guards itself
     for i in (0, 1, 3):
         assert max_rel(got[i].depth, seq(frames[i].cuda()).depth) < 1e-5
+
+
+def _same(a, b):
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+def test_pipelined_predictor_takes_the_callers_objects(ops):
+    """Live objects through the predictor: a graph per slot captured with ``object_capacity``, the objects of [frame | mirrored frame]
+    handed to ``submit`` -- the model's provider is then not asked.  Three steps on two slots (one slot is used twice before
+    ``collect``) == the sequential ``Predictor`` on a graph of the same capacity, whose provider returns the same objects, bit for bit."""
+    from objcavit_amd.graph import GraphedGraphBins
+    from objcavit_amd.predict import PipelinedPredictor, Predictor
+    from test_hip_objects import _objects
+    H, W, N, CAP = 352, 384, 3, 24
+
+    class Scripted:                                         # a "detector" that returns what the test wrote into ``now``
+        now, calls = None, 0
+
+        def __call__(self, image):
+            self.calls += 1
+            return [f.to(image.device) for f in self.now[0]], [b.to(image.device) for b in self.now[1]], None
+
+    m, _, args = _model("graphbins", "nyu", H, W, 29)
+    prov = m.object_provider = Scripted()
+    objs = [_objects([3 + 5 * i, 1 + 7 * i], 70 + i, H, W) for i in range(N)]            # ragged, different for frame and mirror
+    frames = [_frames(80 + i, 1, H, W).cuda() for i in range(N)]
+    gts = [_gt(1, H, W, 90 + i).cuda() for i in range(N)]
+    prov.now = objs[0]
+    example = predict_ref.frames_to_input(frames[0], args, 0, 0, H, W)
+    g = GraphedGraphBins(m, torch.cat([example, example.flip(3)], 0).cuda(), object_capacity=CAP, object_group=1, in_flight=2)
+    seq = Predictor(g, args)
+    ref = []
+    for i in range(N):
+        prov.now = objs[i]
+        r = seq(frames[i], gts[i], first_image_id=i)
+        ref.append((r.depth.clone(), r.records.clone()))
+    assert g.trips == 0
+    pp = PipelinedPredictor(m, args, frames[0], slots=2, object_capacity=CAP)
+    assert len(pp.graphs) == 2 and all(gr.objects is not None for gr in pp.graphs)
+    prov.now, asked = None, prov.calls
+    for i in range(N):
+        pp.submit(frames[i], gts[i], first_image_id=i, object_features=[f.cuda() for f in objs[i][0]],
+                  object_xywh_list=[b.cuda() for b in objs[i][1]])
+    got = pp.collect()
+    assert len(got) == N and pp.rerun_steps == 0 and prov.calls == asked
+    for i in range(N):
+        assert torch.equal(got[i].depth, ref[i][0]) and torch.equal(got[i].records, ref[i][1]), i
+    assert torch.equal(pp.records(got), torch.cat([r[1] for r in ref], 0))
+    assert not torch.equal(ref[0][0], ref[1][0])
+
+
+class _Fp16Only:
+    """A captured graph without its fallback: what the fp16 pairs alone make of a step (no ``checked``, so a sequential step replays it
+    and reads no guard word)."""
+    images_are_independent = True
+
+    def __init__(self, g):
+        self.g, self.static_image, self.object_group = g, g.static_image, g.object_group
+
+    def __call__(self, image):
+        return self.g(image)
+
+
+@pytest.fixture(scope="module")
+def guard_steps(ops):
+    """Five bs-1 steps for a network whose decoder carries a large intermediate (tests/test_hip_fp16_route.py), step 2 the tame frame
+    x 8 after normalisation (see ``test_pipelined_predictor_reruns_a_tripped_step_at_collect`` for the uint8 arithmetic)."""
+    from test_hip_fp16_route import GUARD_SCALE, _guard_alpha, _guard_model
+    H, W, F = 352, 384, 64.0
+    assert GUARD_SCALE == 8.0
+    off = [round(7 * mean * F) for mean in predict_ref.MEAN]
+    frames = []
+    for i in range(5):
+        g = torch.Generator().manual_seed(60 + i)
+        frames.append(torch.stack([torch.randint(-(-c // 8), (255 + c) // 8 + 1, (1, H, W), generator=g) for c in off], 3).to(torch.uint8))
+    args0 = make_args(strategy="learned", language="clip", dimensions_train=[H, W], dimensions_test=[H, W], image_norm_factor=F)
+    alpha = _guard_alpha(ops, predict_ref.frames_to_input(frames[0], args0, 0, 0, H, W), H, W)
+    m, _, args = _guard_model(H, W, alpha=alpha)
+    args["nyu"]["image_norm_factor"] = F
+    m(predict_ref.frames_to_input(frames[0], args, 0, 0, H, W).cuda())       # the model's first batch: calibrates the fp16 pairs
+    big = frames[2].to(torch.int32) * 8 - torch.tensor(off, dtype=torch.int32)
+    assert int(big.min()) >= 0 and int(big.max()) <= 255
+    frames[2] = big.to(torch.uint8)
+    gts = [_gt(1, H, W, 170 + i).cuda() for i in range(5)]
+    return m, args, [f.cuda() for f in frames], [predict_ref.frames_to_input(f, args, 0, 0, H, W).cuda() for f in frames], gts
+
+
+@pytest.mark.parametrize("which", ["PipelinedValidation", "PipelinedPredictor"])
+def test_slot_pipeline_reruns_one_tripped_step_and_forgets_collected_steps(ops, guard_steps, which):
+    """The same scenario through both pipelines: five steps on two slots, step 2 beyond the fp16 pairs' guarded range.  The results
+    come back in submission order; one step is re-run at ``collect()`` and only its result differs from what the fp16-pair graph alone
+    gives (a sequential step on ``_Fp16Only``: same graph shape, same slots in flight, hence the same kernels -- bit for bit); a
+    second ``collect()`` returns the class's empty form; a further submit + collect round returns that one step."""
+    from objcavit_amd.graph import GraphedGraphBins
+    from objcavit_amd.predict import PipelinedPredictor, Predictor
+    from objcavit_amd.validation import PipelinedValidation, ValidationStep
+    m, args, frames, imgs, gts = guard_steps
+    g = _Fp16Only(GraphedGraphBins(m, torch.cat([imgs[0], imgs[0].flip(3)], 0), object_group=1, in_flight=2))
+    if which == "PipelinedValidation":
+        seq, pipe, inputs = ValidationStep(g, args), PipelinedValidation(m, args, imgs[0], slots=2), imgs
+        fp16 = [seq(imgs[i], gts[i], first_image_id=i)[0].clone() for i in range(5)]
+
+        def steps(collected):                               # -> per step, the tensors to compare
+            assert isinstance(collected, torch.Tensor) and collected.device.type == "cuda"
+            return [(r,) for r in collected.split(1)]
+        empty = lambda c: isinstance(c, torch.Tensor) and tuple(c.shape) == (0, 10) and c.device.type == "cpu"
+        fp16 = [(r,) for r in fp16]
+    else:
+        seq, pipe, inputs = Predictor(g, args), PipelinedPredictor(m, args, frames[0], slots=2), frames
+        fp16 = []
+        for i in range(5):
+            r = seq(frames[i], gts[i], first_image_id=i)
+            fp16.append((r.records.clone(), r.depth.clone()))
+
+        def steps(collected):
+            assert isinstance(collected, list)
+            return [(r.records, r.depth) for r in collected]
+        empty = lambda c: c == []
+    assert len(pipe.graphs) == 2 and empty(pipe.collect())
+    for i in range(5):
+        pipe.submit(inputs[i], gts[i], first_image_id=i)
+    got = steps(pipe.collect())
+    assert len(got) == 5 and pipe.rerun_steps == 1
+    assert [int(s[0][0, 9]) for s in got] == list(range(5))                 # image ids: submission order
+    for i in range(5):
+        same = all(_same(a, b) for a, b in zip(got[i], fp16[i]))
+        assert same == (i != 2), i
+        assert all(bool(torch.isfinite(t).all()) for t in got[i]), i
+    assert empty(pipe.collect()) and pipe.rerun_steps == 1
+    pipe.submit(inputs[1], gts[1], first_image_id=1)
+    again = steps(pipe.collect())
+    assert len(again) == 1 and all(_same(a, b) for a, b in zip(again[0], fp16[1])) and pipe.rerun_steps == 1
+    assert empty(pipe.collect())
