@@ -692,6 +692,25 @@ int ocv_depth_finalize_fwd(const float* pred, const float* pred_mirror, int h, i
 int ocv_depth_finalize_stats_fwd(const float* pred, const float* pred_mirror, const float* var, const float* var_mirror,
                                  const float* pmax, const float* pmax_mirror, int h, int w, float min_depth, float max_depth, int H, int W,
                                  float* depth_std, float* confidence, int B, ocv_stream_t stream);
+/* Per-object readout of the final map: depth statistics per detection box (no counterpart in the reference; the statement the tests
+ * compare against is tests/object_depth_ref.py).  depth [B][1][H][W] fp32 (the map of ocv_depth_finalize_fwd), depth_std the same shape
+ * or null; box r of image b = xywh[(b * cap + r) * xywh_row_stride + 0..3] = centre x, centre y, width, height in pixels of the map's
+ * grid; counts int32 [B] in DEVICE memory, read by the kernel only (capturable: a replay serves whatever the buffers hold).
+ * Pixel (x, y) belongs to a box iff its centre (x + 0.5, y + 0.5) lies in [cx - hw, cx + hw) x [cy - hh, cy + hh), in fp32 and in this
+ * order: hw = half * w (half = fp32(0.5 * shrink), 0 < shrink <= 1 reads the central part of the box), x0 = ceil((cx - hw) - 0.5),
+ * x1 = ceil((cx + hw) - 0.5); non-finite -> empty; both clamped to [0, W]; columns x0 .. x1 - 1; rows alike from cy, h, H.
+ * out [B][cap][5 + Q] fp32, v = the non-NaN values of the box's pixels in ascending order (+-inf take part):
+ *   0 n         their number (exact below 2^24)        1 min = v[0]        2 max = v[n - 1]
+ *   3 mean      float64 sum of v / n, rounded to fp32
+ *   4 std_mean  the same mean of depth_std over the same pixels (0 without depth_std)
+ *   5 + i       v[floor(quantiles[i] * (n - 1))], product and floor in double: an ELEMENT of the map, never interpolated (0.5: the
+ *               lower median, torch.median's); -0 and +0 are one value and either may be returned
+ * Every column is 0 for a row at or beyond counts[b] and for a row whose pixel set is empty or all NaN: n = 0 is the flag.  Every
+ * element of out is written.  quantiles: HOST array of Q doubles in [0, 1], 1 <= Q <= 8, copied by value into the launch.
+ * One launch of B * cap workgroups (exact radix select, 4 reads of a box's pixels), no workspace, no allocation, no synchronisation, no
+ * float atomics: two calls give bit-equal output. */
+int ocv_object_depth_fwd(const float* depth, const float* depth_std, const float* xywh, long xywh_row_stride, const int* counts, int B,
+                         int cap, int H, int W, float half, const double* quantiles, int Q, float* out, ocv_stream_t stream);
 
 /* Tail of mViT / ObjCAViT.forward + glue of AdaBins / GraphBins.forward in one launch (modules/miniViT.py:33-42, modules/AdaBins.py:79-83):
  *   y = raw [B][n_bins] (the regressor's last Linear) -> OCV_BINNORM_LINEAR: relu(y) + 0.1 | OCV_BINNORM_SIGMOID: sigmoid(y) |

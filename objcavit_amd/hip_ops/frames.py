@@ -4,7 +4,8 @@ maps out (csrc/depth_finalize.hip).  Same rules as every wrapper: operands are c
 static input)."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import ctypes as C
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -194,4 +195,50 @@ def depth_finalize(pred: torch.Tensor, min_depth: float, max_depth: float, size:
     return res
 
 
-__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale"]
+OBJECT_DEPTH_COLUMNS = 5          # n, min, max, mean, std_mean in front of the quantiles
+
+
+def object_depth(depth: torch.Tensor, xywh: torch.Tensor, counts: torch.Tensor, depth_std: Optional[torch.Tensor] = None,
+                 quantiles: Sequence[float] = (0.1, 0.5, 0.9), shrink: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depth statistics per detection box: ``depth`` fp32 [B, 1, H, W] (the final map), ``xywh`` fp32 [B, cap, k >= 4] = centre x,
+    centre y, width, height in the map's pixels (rows may be wider than 4 and strided: ``PaddedObjects.xywh``), ``counts`` int32 [B] on
+    the device -> fp32 [B, cap, 5 + Q]: n, min, max, mean, std_mean, then v[floor(q * (n - 1))] per quantile, v the sorted non-NaN
+    pixels whose centres lie inside the box (its central ``shrink`` part).  min, max and the quantiles are elements of the map; the
+    means are float64 sums rounded once; std_mean is the mean of ``depth_std`` (same shape as ``depth``) over the same pixels, 0
+    without it.  Rows at or beyond ``counts[b]`` and boxes without a valid pixel are all zero (n = 0).  One launch
+    (ocv_object_depth_fwd), the counts are read on the device only."""
+    lib = _lib.load()
+    _req(depth, "depth")
+    if depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError(f"object_depth: expected depth [B, 1, H, W], got {tuple(depth.shape)}")
+    B, _, H, W = (int(s) for s in depth.shape)
+    if depth_std is not None:
+        _req(depth_std, "depth_std")
+        if depth_std.shape != depth.shape:
+            raise ValueError("object_depth: depth_std must have depth's shape")
+    _req(xywh, "xywh", contiguous=False)
+    if xywh.dim() != 3 or xywh.shape[0] != B or xywh.shape[1] < 1 or xywh.shape[2] < 4:
+        raise ValueError(f"object_depth: expected xywh [{B}, cap >= 1, k >= 4], got {tuple(xywh.shape)}")
+    cap = int(xywh.shape[1])
+    st = xywh.stride()
+    row = int(st[1]) if cap > 1 else max(int(st[1]), 4)
+    if st[2] != 1 or row < 4 or (B > 1 and st[0] != cap * row):
+        raise ValueError(f"object_depth: xywh rows must be dense and evenly spaced over the batch (strides {st})")
+    _req(counts, "counts", torch.int32)
+    if tuple(counts.shape) != (B,):
+        raise ValueError(f"object_depth: counts must be int32 [{B}], got {tuple(counts.shape)}")
+    q = tuple(float(v) for v in quantiles)
+    if not 1 <= len(q) <= 8 or not all(0.0 <= v <= 1.0 for v in q):
+        raise ValueError(f"object_depth: 1 to 8 quantiles in [0, 1], got {q}")
+    shrink = float(shrink)
+    if not 0.0 < shrink <= 1.0 or C.c_float(0.5 * shrink).value <= 0.0:
+        raise ValueError(f"object_depth: shrink must be in (0, 1], got {shrink}")
+    out = _out_slice(out, (B, cap, OBJECT_DEPTH_COLUMNS + len(q)), torch.float32, depth.device, "object_depth")
+    with timed("object_depth"):
+        check(lib.ocv_object_depth_fwd(depth.data_ptr(), _ptr(depth_std), xywh.data_ptr(), row, counts.data_ptr(), B, cap, H, W,
+                                       0.5 * shrink, (C.c_double * len(q))(*q), len(q), out.data_ptr(), _stream()),
+              "ocv_object_depth_fwd")
+    return out
+
+
+__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS"]

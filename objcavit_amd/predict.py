@@ -20,6 +20,7 @@ import torch
 
 from . import hip_ops
 from ._lib import HipLibraryError
+from .object_depth import DEFAULT_QUANTILES, ObjectDepths, object_depths, pad_boxes
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
@@ -31,6 +32,23 @@ STATS_WANT = ("depth_std", "confidence")       # the outputs that need the model
 
 PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "records", "bin_edges", "depth_std", "confidence"],
                            defaults=(None, None))
+PredictResult.objects = None                   # the per-object readout (an ``ObjectDepths``) or None: an ATTRIBUTE, not a field
+
+
+class _ObjectsResult(PredictResult):
+    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` attribute holds the step's ``ObjectDepths``."""
+
+    def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, **kw):
+        self = super().__new__(cls, *fields, **kw)
+        self.objects = objects
+        return self
+
+    def _replace(self, **kw):
+        return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects)
+
+
+# what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth and readout boxes
+_Step = namedtuple("_Step", ["depth_gt", "boxes"])
 
 Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
 
@@ -72,6 +90,17 @@ def colormap_table(name: str = "inferno_r") -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(lut)).to(torch.uint8)
 
 
+def _readout_options(object_depth) -> Optional[dict]:
+    """The ``object_depth`` keyword of both predictors: None (no readout) or a dict with some of ``quantiles`` / ``shrink``."""
+    if object_depth is None:
+        return None
+    opts = dict(object_depth)
+    bad = set(opts) - {"quantiles", "shrink"}
+    if bad:
+        raise ValueError(f"object_depth: unknown option(s) {sorted(bad)}; expected some of 'quantiles', 'shrink'")
+    return {"quantiles": tuple(opts.get("quantiles", DEFAULT_QUANTILES)), "shrink": float(opts.get("shrink", 1.0))}
+
+
 def _window(args, Hs: int, Ws: int, crop) -> Tuple[int, int, int, int]:
     """(top, left, H, W): ``crop`` as given, else the dataset's rule -- the KITTI benchmark crop with ``do_kb_crop``, else the frame."""
     if crop is not None:
@@ -101,8 +130,9 @@ def _frame_list(frames: Frames, what: str, dims: int) -> List[torch.Tensor]:
 class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
-    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop):
+    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
+        self.readout = _readout_options(object_depth)
         self.min_depth, self.max_depth = _depth_range(args)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
@@ -168,10 +198,23 @@ class _Ends:
             i += int(m.shape[0])
         return out
 
+    def boxes_on(self, boxes, device, B: int):
+        """The readout boxes of a step as (xywh, counts) on the device, or None without the ``object_depth`` keyword / without boxes."""
+        if self.readout is None or boxes is None:
+            return None
+        xywh, counts = pad_boxes(boxes, device)
+        if xywh.dim() != 3 or int(xywh.shape[0]) != B or tuple(counts.shape) != (B,):
+            raise ValueError(f"boxes: one entry per un-mirrored frame ({B}), got xywh {tuple(xywh.shape)} / counts {tuple(counts.shape)}")
+        return xywh, counts
+
     def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int,
-               want: Tuple[str, ...]) -> PredictResult:
+               want: Tuple[str, ...], boxes=None) -> PredictResult:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
-        the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence"."""
+        the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  ``boxes``
+        (``boxes_on``'s pair): the per-object readout right behind the final map, which is then made even if ``want`` leaves it out."""
+        asked = want
+        if boxes is not None and "depth" not in want:
+            want = want + ("depth",)
         pred = out.depth_pred.contiguous()
         mirror_pred = None if mirror is None else mirror.depth_pred.contiguous()
         edges = getattr(out, "bin_edges", None)
@@ -186,8 +229,11 @@ class _Ends:
         rec = None
         if depth_gt is not None:
             rec = _records(pred, mirror_pred, edges, depth_gt, self.args, self.min_depth, self.max_depth, first_image_id, self.loss)
-        return PredictResult(maps.get("depth"), maps.get("depth_u16"), maps.get("rgb8"), rec, edges, maps.get("depth_std"),
-                             maps.get("confidence"))
+        res = PredictResult(maps.get("depth") if "depth" in asked else None, maps.get("depth_u16"), maps.get("rgb8"), rec, edges,
+                            maps.get("depth_std"), maps.get("confidence"))
+        if boxes is None:
+            return res
+        return _ObjectsResult(*res, objects=object_depths(maps["depth"], boxes, depth_std=maps.get("depth_std"), **self.readout))
 
 
 def _need_stats(want) -> bool:
@@ -230,12 +276,19 @@ class Predictor:
     ``records``: the [B, 10] / [B, 16] table of ``ValidationStep`` when ground
     truth is given; ``bin_edges``: those of the un-mirrored forward (a captured graph hands out its static tensor).
     ``model``: GraphBins / AdaBins, or a ``GraphedGraphBins`` captured for the [batch | mirrored batch] shape with
-    ``object_group = B`` -- the frames are then ingested straight into its static input and it is called through ``checked``."""
+    ``object_group = B`` -- the frames are then ingested straight into its static input and it is called through ``checked``.
+    ``object_depth``: None, or a dict with some of ``quantiles`` / ``shrink`` -- the per-object readout (objcavit_amd/object_depth.py).
+    With it, ``boxes=`` of a call -- the boxes a detector found in the B frames, in pixels of the cropped window: a list of [N_i, >= 4]
+    tensors / None, an (xywh, counts) pair or a ``PaddedObjects``; independent of the objects the model's provider is fed -- is read out
+    of the final map by one launch behind the finalize launch, and the result's ``objects`` ATTRIBUTE holds the ``ObjectDepths`` (None
+    otherwise; ``PredictResult``'s fields are what they were).  The fp32 map is made for it even when ``want`` leaves "depth" out;
+    ``std_mean`` is filled when ``want`` names "depth_std"."""
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
-                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None):
+                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None,
+                 object_depth: Optional[dict] = None):
         self.model = model
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -248,7 +301,8 @@ class Predictor:
         return _forward_pair(self.model, both=self.ends.ingest(frames, out=static if fits and _joint(self.model, B) else None))
 
     @torch.no_grad()
-    def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",)) -> PredictResult:
+    def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",),
+                 boxes=None) -> PredictResult:
         want = _check_want(want)
         if _need_stats(want):
             _turn_stats_on(self.model)
@@ -256,7 +310,8 @@ class Predictor:
         B = sum(int(f.shape[0]) for f in frames)
         size = self.ends.window_of(frames)
         out, mirror = self._forward(frames, B)
-        return self.ends.finish(out, mirror, size, self.ends.ground_truth(depth_gt, B), first_image_id, want)
+        return self.ends.finish(out, mirror, size, self.ends.ground_truth(depth_gt, B), first_image_id, want,
+                                self.ends.boxes_on(boxes, frames[0].device, B))
 
 
 class PipelinedPredictor(_SlotPipeline):
@@ -267,7 +322,8 @@ class PipelinedPredictor(_SlotPipeline):
     stream; ``collect`` returns the ``PredictResult`` of every submitted step in submission order; a step whose fp16 range guard
     tripped is ingested again from its kept frames for the re-run.  ``bin_edges`` of a result is
     None unless ``want`` names "bin_edges" (the graph's static tensor is then copied per step).  Wants ``GPU_MAX_HW_QUEUES`` >= slots
-    set before the HIP runtime starts, like ``PipelinedValidation``.
+    set before the HIP runtime starts, like ``PipelinedValidation``.  ``object_depth`` / ``submit(..., boxes=)``: as ``Predictor``'s; the
+    readout runs on the slot's stream, a re-run step is read out from the re-run's map.
 
         pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
         for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
@@ -280,13 +336,13 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
-                 crop: Optional[Tuple[int, int, int, int]] = None):
+                 crop: Optional[Tuple[int, int, int, int]] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
         if _need_stats(self.want):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth)
         self.flip_tta = flip_tta
         ex = _frame_list(example_frames, "example_frames", 4)
         self.B = sum(int(f.shape[0]) for f in ex)
@@ -302,23 +358,27 @@ class PipelinedPredictor(_SlotPipeline):
     def _restage(self, frames: List[torch.Tensor]) -> torch.Tensor:
         return self.ends.ingest(frames)                      # the slot's static input has long been overwritten: ingest again
 
-    def _finish(self, out, depth_gt, first_image_id: int) -> PredictResult:
-        gt = self.ends.ground_truth(depth_gt, self.B)
+    def _finish(self, out, step: _Step, first_image_id: int) -> PredictResult:
+        gt = self.ends.ground_truth(step.depth_gt, self.B)
         out, mirror = _split(out, self.B) if self.flip_tta else (out, None)
-        res = self.ends.finish(out, mirror, self.size, gt, first_image_id, self.want)
+        res = self.ends.finish(out, mirror, self.size, gt, first_image_id, self.want, step.boxes)
         return res._replace(bin_edges=res.bin_edges.clone() if (self.want_edges and res.bin_edges is not None) else None)
 
     def collect(self) -> List[PredictResult]:
         """Wait for every submitted step; -> their results in submission order (and forget them)."""
         return self._collect()
 
-    def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None) -> None:
-        """Enqueue one predict step on the next slot's stream; returns at once."""
+    def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None,
+               boxes=None) -> None:
+        """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the readout boxes of the step's frames
+        (``object_depth`` keyword); lists are padded here, on the caller's stream, and the tensors are held like the frames."""
         frames = _frame_list(frames_u8, "frames_u8", 4)
         if sum(int(f.shape[0]) for f in frames) != self.B or self.ends.window_of(frames) != self.size:
             raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")
         held = list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
-        self._submit(frames, held, depth_gt, first_image_id, (object_features, object_xywh_list))
+        boxes = self.ends.boxes_on(boxes, frames[0].device, self.B)
+        held += list(boxes or ())
+        self._submit(frames, held, _Step(depth_gt, boxes), first_image_id, (object_features, object_xywh_list))
 
     def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
         """The record table [N * B, 10] ([N * B, 16] with ``loss``) of collected results that carried ground truth."""
