@@ -711,6 +711,35 @@ int ocv_depth_finalize_stats_fwd(const float* pred, const float* pred_mirror, co
  * float atomics: two calls give bit-equal output. */
 int ocv_object_depth_fwd(const float* depth, const float* depth_std, const float* xywh, long xywh_row_stride, const int* counts, int B,
                          int cap, int H, int W, float half, const double* quantiles, int Q, float* out, ocv_stream_t stream);
+/* Point-cloud output of the final map: a deterministic, filtered stream compaction with a pinhole back-projection (no counterpart in the
+ * reference, which only carries the focal length with every sample; the statement the tests compare against is tests/point_cloud_ref.py).
+ * depth [B][1][H][W] fp32 (the map of ocv_depth_finalize_fwd); K [B][4] fp32 in DEVICE memory = fx, fy, cx, cy in pixels of the map's own
+ * grid, OpenCV convention (the integer index (x, y) is the pixel's centre; the caller shifts the principal point by the crop origin);
+ * confidence / depth_std: the same shape as depth, or null; frames: null, or uint8 [B][Hs][Ws][3] with byte strides frame_stride /
+ * row_stride (as ocv_frame_ingest_fwd takes them) of which the H x W window at (top, left) is the map's grid.
+ * Pixel (x, y) of image b is KEPT iff  y % sy == 0 and x % sx == 0;  z = depth[b][0][y][x] is finite and near <= z <= far;  with a
+ * confidence map conf >= min_confidence (NaN fails);  with a std map std <= max_std (NaN fails);  and fx, fy are finite and > 0 and
+ * cx, cy finite (else the image keeps nothing).  Kept pixels are numbered in row-major order of (y, x); point i is the i-th kept pixel.
+ * Record i of image b = points[(b * cap + i) * 4 .. + 4), 16 bytes written by one store:
+ *   bytes 0-11  X, Y, Z fp32, every operation rounded on its own:  rx = (float(x) - cx) / fx,  ry = (float(y) - cy) / fy (IEEE
+ *               division),  X = rx * z,  Y = ry * z,  Z = z
+ *   bytes 12-14 R, G, B of frames[b][top + y][left + x]; 0 without frames
+ *   byte 15     rint(255 * clamp(conf, 0, 1)), ties to even; 255 without a confidence map
+ * pixel: null, or int32 [B][cap] = y * W + x of every point.  total int32 [B] = number of kept pixels; counts int32 [B] = min(total, cap):
+ * with total > cap the first cap points in order are written.  Rows of points / pixel at or beyond counts[b] are NOT WRITTEN (they keep
+ * whatever the buffer held: a multi-megabyte tail per image is not zeroed).  points and K 16-byte aligned.
+ * workspace: ocv_depth_unproject_workspace_bytes = B * T * 4 bytes, T = ceil(ceil(H / sy) * ceil(W / sx) / OCV_UNPROJECT_TILE) tiles per
+ * image (0 for sizes the entry point refuses).  Two launches on the stream (count per tile; prefix + write) and nothing else: no
+ * allocation, no synchronisation, no atomics, nothing read on the host (capturable); two calls give identical bytes.  Images are
+ * independent: a batch can be filled by one call per image with offset pointers.
+ * -1 with a message before any launch on: a null required pointer, bad sizes, a stride < 1, cap < 1, near > far (or NaN), a window that
+ * does not fit the frame, a workspace that is too small, misaligned pointers. */
+#define OCV_UNPROJECT_TILE 2048
+size_t ocv_depth_unproject_workspace_bytes(int B, int H, int W, int sy, int sx);
+int ocv_depth_unproject_fwd(const float* depth, const float* K, const float* confidence, const float* depth_std, const uint8_t* frames,
+                            long frame_stride, long row_stride, int Hs, int Ws, int top, int left, int B, int H, int W, int sy, int sx,
+                            float near, float far, float min_confidence, float max_std, int cap, float* points, int* pixel, int* counts,
+                            int* total, void* workspace, size_t workspace_bytes, ocv_stream_t stream);
 
 /* Tail of mViT / ObjCAViT.forward + glue of AdaBins / GraphBins.forward in one launch (modules/miniViT.py:33-42, modules/AdaBins.py:79-83):
  *   y = raw [B][n_bins] (the regressor's last Linear) -> OCV_BINNORM_LINEAR: relu(y) + 0.1 | OCV_BINNORM_SIGMOID: sigmoid(y) |

@@ -1,5 +1,6 @@
 """hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip), full-resolution depth
-maps out (csrc/depth_finalize.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
+maps out (csrc/depth_finalize.hip), and what is read out of the final map behind them: per-box statistics (csrc/object_depth.hip) and the
+point cloud (csrc/point_cloud.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
 static input)."""
 from __future__ import annotations
@@ -241,4 +242,96 @@ def object_depth(depth: torch.Tensor, xywh: torch.Tensor, counts: torch.Tensor, 
     return out
 
 
-__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS"]
+UNPROJECT_TILE = 2048             # include/objcavit_hip.h: OCV_UNPROJECT_TILE, candidates of the strided grid per workgroup
+
+
+def unproject_grid(H: int, W: int, stride: Tuple[int, int] = (1, 1)) -> Tuple[int, int]:
+    """(rows, columns) of the strided pixel grid of an H x W map: the pixels with y % sy == 0 and x % sx == 0."""
+    sy, sx = int(stride[0]), int(stride[1])
+    if sy < 1 or sx < 1:
+        raise ValueError(f"depth_unproject: stride must be >= 1, got {tuple(stride)}")
+    return -(-int(H) // sy), -(-int(W) // sx)
+
+
+def depth_unproject(depth: torch.Tensor, K: torch.Tensor, capacity: int, stride: Tuple[int, int] = (1, 1), near: float = 0.0,
+                    far: float = float("inf"), confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0,
+                    depth_std: Optional[torch.Tensor] = None, max_std: float = float("inf"), frames: Optional[torch.Tensor] = None,
+                    top: int = 0, left: int = 0, want_pixel: bool = False, out: Optional[dict] = None,
+                    workspace: Optional[torch.Tensor] = None, image_index: int = 0) -> dict:
+    """The final map as 3-D points in the camera frame: ``depth`` fp32 [B, 1, H, W], ``K`` fp32 [B, 4] on the device = fx, fy, cx, cy in
+    pixels of the map's grid (OpenCV convention: index (x, y) is the pixel's centre) -> {"points": fp32 [B, capacity, 4], "counts": int32
+    [B], "total": int32 [B]} (+ "pixel": int32 [B, capacity] = y * W + x with ``want_pixel``).  A pixel is kept iff it lies on the
+    ``stride`` = (sy, sx) grid, its depth z is finite with near <= z <= far, ``confidence`` >= min_confidence and ``depth_std`` <= max_std
+    where those maps (depth's shape) are given (NaN fails), and the image's fx, fy are finite and > 0, cx, cy finite.  Kept pixels are
+    numbered in row-major order; point i is a 16-byte record: X = ((x - cx) / fx) * z, Y = ((y - cy) / fy) * z, Z = z (fp32, every
+    operation rounded on its own), then the bytes R, G, B of ``frames[b, top + y, left + x]`` (uint8 [B, Hs, Ws, 3], rows / frames may be
+    strided as ``frame_ingest`` takes them; 0 without frames) and rint(255 * clamp(confidence, 0, 1)) (255 without the map).
+    total = the number of kept pixels, counts = min(total, capacity): the first ``capacity`` points are written.  ROWS AT OR BEYOND
+    counts[b] ARE NOT WRITTEN: they hold whatever the buffer held (a new tensor: uninitialised memory) -- read ``points[b, :counts[b]]``.
+    ``out``: {name: tensor} of caller-owned buffers [N, ...] with N >= image_index + B; the B images are written at ``image_index``
+    (one batch filled by one call per differently sized frame) and the dict returned holds the whole buffers.  ``workspace``: a uint8
+    device tensor of at least ``ocv_depth_unproject_workspace_bytes`` (default: the stream's workspace store).  Two launches
+    (ocv_depth_unproject_fwd) on the current stream, nothing read on the host: capturable with ``out`` and a warmed-up workspace."""
+    lib = _lib.load()
+    _req(depth, "depth")
+    if depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError(f"depth_unproject: expected depth [B, 1, H, W], got {tuple(depth.shape)}")
+    B, _, H, W = (int(s) for s in depth.shape)
+    _req(K, "K")
+    if tuple(K.shape) != (B, 4):
+        raise ValueError(f"depth_unproject: K must be fp32 [{B}, 4] = fx, fy, cx, cy, got {tuple(K.shape)}")
+    for name, t in (("confidence", confidence), ("depth_std", depth_std)):
+        if t is not None:
+            _req(t, name)
+            if t.shape != depth.shape:
+                raise ValueError(f"depth_unproject: {name} must have depth's shape")
+    sy, sx = int(stride[0]), int(stride[1])
+    unproject_grid(H, W, (sy, sx))
+    cap = int(capacity)
+    if cap < 1:
+        raise ValueError(f"depth_unproject: capacity must be >= 1, got {capacity}")
+    if not float(near) <= float(far):
+        raise ValueError(f"depth_unproject: near = {near} must be <= far = {far}")
+    fs = rs = Hs = Ws = 0
+    if frames is not None:
+        Bf, Hs, Ws, fs, rs = _frames_view(frames, "frames", torch.uint8, 3)
+        if Bf != B:
+            raise ValueError(f"depth_unproject: {Bf} frame(s) for {B} map(s)")
+        _window(Hs, Ws, int(top), int(left), (H, W), "depth_unproject")
+    out = dict(out or {})
+    names = ("points", "counts", "total") + (("pixel",) if want_pixel else ())
+    shapes = {"points": (cap, 4), "counts": (), "total": (), "pixel": (cap,)}
+    N, index = B, int(image_index)
+    if out:
+        given = out.get("points")
+        if not isinstance(given, torch.Tensor) or given.dim() != 3:
+            raise ValueError("depth_unproject: out needs 'points' [N, capacity, 4]")
+        N = int(given.shape[0])
+        if index < 0 or index + B > N:
+            raise ValueError(f"depth_unproject: {B} image(s) at index {index} do not fit buffers of {N}")
+    else:
+        index = 0
+    res = {}
+    for name in names:
+        dtype = torch.float32 if name == "points" else torch.int32
+        if out and name not in out:
+            raise ValueError(f"depth_unproject: out has no '{name}' (it needs {names})")
+        res[name] = _out_slice(out.get(name), (N,) + shapes[name], dtype, depth.device, "depth_unproject")
+    need = int(lib.ocv_depth_unproject_workspace_bytes(B, H, W, sy, sx))
+    if workspace is None:
+        from ._core import workspace as _workspace
+        workspace = _workspace(need, depth.device, "depth_unproject")
+    else:
+        _req(workspace, "workspace", torch.uint8)
+    with timed("depth_unproject"):
+        check(lib.ocv_depth_unproject_fwd(depth.data_ptr(), K.data_ptr(), _ptr(confidence), _ptr(depth_std), _ptr(frames), fs, rs, Hs, Ws,
+                                          int(top), int(left), B, H, W, sy, sx, float(near), float(far), float(min_confidence),
+                                          float(max_std), cap, res["points"].data_ptr() + 16 * cap * index,
+                                          res["pixel"].data_ptr() + 4 * cap * index if want_pixel else None,
+                                          res["counts"].data_ptr() + 4 * index, res["total"].data_ptr() + 4 * index,
+                                          workspace.data_ptr(), int(workspace.numel()), _stream()), "ocv_depth_unproject_fwd")
+    return res
+
+
+__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "depth_unproject",
+           "unproject_grid", "UNPROJECT_TILE"]

@@ -21,6 +21,7 @@ import torch
 from . import hip_ops
 from ._lib import HipLibraryError
 from .object_depth import DEFAULT_QUANTILES, ObjectDepths, object_depths, pad_boxes
+from .point_cloud import PointCloud
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
@@ -33,22 +34,26 @@ STATS_WANT = ("depth_std", "confidence")       # the outputs that need the model
 PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "records", "bin_edges", "depth_std", "confidence"],
                            defaults=(None, None))
 PredictResult.objects = None                   # the per-object readout (an ``ObjectDepths``) or None: an ATTRIBUTE, not a field
+PredictResult.points = None                    # the point cloud (a ``PointCloud``) or None: an attribute as well
 
 
 class _ObjectsResult(PredictResult):
-    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` attribute holds the step's ``ObjectDepths``."""
+    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` attributes hold the step's ``ObjectDepths`` /
+    ``PointCloud``."""
 
-    def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, **kw):
+    def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, points: Optional[PointCloud] = None, **kw):
         self = super().__new__(cls, *fields, **kw)
         self.objects = objects
+        self.points = points
         return self
 
     def _replace(self, **kw):
-        return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects)
+        return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects, points=self.points)
 
 
-# what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth and readout boxes
-_Step = namedtuple("_Step", ["depth_gt", "boxes"])
+# what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth, its readout
+# boxes and, for the point cloud, its intrinsics (of the source frames, on the device)
+_Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics"], defaults=(None,))
 
 Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
 
@@ -101,6 +106,41 @@ def _readout_options(object_depth) -> Optional[dict]:
     return {"quantiles": tuple(opts.get("quantiles", DEFAULT_QUANTILES)), "shrink": float(opts.get("shrink", 1.0))}
 
 
+_CLOUD_KEYS = ("stride", "near", "far", "min_confidence", "max_std", "capacity", "colour", "pixel")
+
+
+def _cloud_options(point_cloud, min_depth: float, max_depth: float) -> Optional[dict]:
+    """The ``point_cloud`` keyword of both predictors: None (no cloud) or a dict with some of ``_CLOUD_KEYS``.  Defaults: every pixel
+    (stride (1, 1)) within the dataset's depth range, no uncertainty filter, capacity = the strided grid's size (None here: the map's
+    size is known at the call), the frame's colour in every record, no pixel index."""
+    if point_cloud is None:
+        return None
+    opts = dict(point_cloud)
+    bad = set(opts) - set(_CLOUD_KEYS)
+    if bad:
+        raise ValueError(f"point_cloud: unknown option(s) {sorted(bad)}; expected some of {_CLOUD_KEYS}")
+    stride = opts.get("stride", (1, 1))
+    stride = (int(stride), int(stride)) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
+    hip_ops.unproject_grid(1, 1, stride)
+    cap = opts.get("capacity")
+    if cap is not None and int(cap) < 1:
+        raise ValueError(f"point_cloud: capacity must be >= 1, got {cap}")
+    out = {"stride": stride, "near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth)),
+           "min_confidence": float(opts.get("min_confidence", 0.0)), "max_std": float(opts.get("max_std", float("inf"))),
+           "capacity": None if cap is None else int(cap), "colour": bool(opts.get("colour", True)), "pixel": bool(opts.get("pixel", False))}
+    if not out["near"] <= out["far"]:
+        raise ValueError(f"point_cloud: near = {out['near']} must be <= far = {out['far']}")
+    return out
+
+
+def _cloud_want(cloud: Optional[dict]) -> Tuple[str, ...]:
+    """The maps a point cloud's filters read beyond "depth": they are made for it (and ``bin_stats`` turned on) even when ``want``
+    leaves them out."""
+    if cloud is None:
+        return ()
+    return (("confidence",) if cloud["min_confidence"] > 0.0 else ()) + (("depth_std",) if cloud["max_std"] < float("inf") else ())
+
+
 def _window(args, Hs: int, Ws: int, crop) -> Tuple[int, int, int, int]:
     """(top, left, H, W): ``crop`` as given, else the dataset's rule -- the KITTI benchmark crop with ``do_kb_crop``, else the frame."""
     if crop is not None:
@@ -130,10 +170,11 @@ def _frame_list(frames: Frames, what: str, dims: int) -> List[torch.Tensor]:
 class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
-    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None):
+    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.readout = _readout_options(object_depth)
         self.min_depth, self.max_depth = _depth_range(args)
+        self.cloud = _cloud_options(point_cloud, self.min_depth, self.max_depth)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -207,14 +248,62 @@ class _Ends:
             raise ValueError(f"boxes: one entry per un-mirrored frame ({B}), got xywh {tuple(xywh.shape)} / counts {tuple(counts.shape)}")
         return xywh, counts
 
+    def intrinsics_on(self, intrinsics, device, B: int) -> Optional[torch.Tensor]:
+        """The intrinsics of a step -- a [B, 4] tensor or a list of per-frame 4-vectors, fx, fy, cx, cy in pixels of the SOURCE frames --
+        as fp32 [B, 4] on the device, or None without the ``point_cloud`` keyword / without intrinsics."""
+        if self.cloud is None or intrinsics is None:
+            return None
+        if not isinstance(intrinsics, torch.Tensor):
+            intrinsics = torch.stack([torch.as_tensor(k, dtype=torch.float32).reshape(-1).cpu() for k in intrinsics], 0)
+        if tuple(intrinsics.shape) != (B, 4):
+            raise ValueError(f"intrinsics: one (fx, fy, cx, cy) per frame ([{B}, 4]), got {tuple(intrinsics.shape)}")
+        return intrinsics.to(device=device, dtype=torch.float32).contiguous()
+
+    def _shift(self, device, top: int, left: int) -> torch.Tensor:
+        ent = self._on(device, False)
+        key = ("shift", top, left)
+        if key not in ent:
+            ent[key] = torch.tensor([0.0, 0.0, float(left), float(top)], dtype=torch.float32, device=device)
+        return ent[key]
+
+    def points_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor]) -> PointCloud:
+        """The point cloud of a step's final map: one launch pair per entry of ``frames`` (a list of differently sized frames has an
+        origin -- hence a principal point -- and a colour source per frame) into one set of buffers.  K is shifted by each frame's
+        window origin (``point_cloud.shift_intrinsics``'s statement, the offsets cached on the device)."""
+        c, depth = self.cloud, maps["depth"]
+        B, _, H, W = (int(v) for v in depth.shape)
+        gh, gw = hip_ops.unproject_grid(H, W, c["stride"])
+        cap = gh * gw if c["capacity"] is None else c["capacity"]
+        dev = depth.device
+        bufs = {"points": torch.empty((B, cap, 4), dtype=torch.float32, device=dev),
+                "counts": torch.empty((B,), dtype=torch.int32, device=dev), "total": torch.empty((B,), dtype=torch.int32, device=dev)}
+        if c["pixel"]:
+            bufs["pixel"] = torch.empty((B, cap), dtype=torch.int32, device=dev)
+        conf = maps.get("confidence")
+        std = maps.get("depth_std") if c["max_std"] < float("inf") else None
+        i = 0
+        for f in frames:
+            n = int(f.shape[0])
+            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
+            hip_ops.depth_unproject(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), cap, stride=c["stride"], near=c["near"],
+                                    far=c["far"], confidence=None if conf is None else conf[i:i + n], min_confidence=c["min_confidence"],
+                                    depth_std=None if std is None else std[i:i + n], max_std=c["max_std"],
+                                    frames=f if c["colour"] else None, top=top, left=left, want_pixel=c["pixel"], out=bufs, image_index=i)
+            i += n
+        return PointCloud(bufs["points"], bufs["counts"], bufs["total"], bufs.get("pixel"))
+
     def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int,
-               want: Tuple[str, ...], boxes=None) -> PredictResult:
+               want: Tuple[str, ...], boxes=None, cloud=None) -> PredictResult:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
         the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  ``boxes``
-        (``boxes_on``'s pair): the per-object readout right behind the final map, which is then made even if ``want`` leaves it out."""
+        (``boxes_on``'s pair): the per-object readout right behind the final map, which is then made even if ``want`` leaves it out.
+        ``cloud`` = (K of the source frames [B, 4], the frames): the point cloud behind the map (and behind the readout), with the
+        maps its filters read made likewise."""
         asked = want
-        if boxes is not None and "depth" not in want:
+        if (boxes is not None or cloud is not None) and "depth" not in want:
             want = want + ("depth",)
+        if cloud is not None:
+            want = want + tuple(w for w in _cloud_want(self.cloud) if w not in want)
         pred = out.depth_pred.contiguous()
         mirror_pred = None if mirror is None else mirror.depth_pred.contiguous()
         edges = getattr(out, "bin_edges", None)
@@ -230,10 +319,14 @@ class _Ends:
         if depth_gt is not None:
             rec = _records(pred, mirror_pred, edges, depth_gt, self.args, self.min_depth, self.max_depth, first_image_id, self.loss)
         res = PredictResult(maps.get("depth") if "depth" in asked else None, maps.get("depth_u16"), maps.get("rgb8"), rec, edges,
-                            maps.get("depth_std"), maps.get("confidence"))
-        if boxes is None:
+                            maps.get("depth_std") if "depth_std" in asked else None,
+                            maps.get("confidence") if "confidence" in asked else None)
+        if boxes is None and cloud is None:
             return res
-        return _ObjectsResult(*res, objects=object_depths(maps["depth"], boxes, depth_std=maps.get("depth_std"), **self.readout))
+        objects = None
+        if boxes is not None:
+            objects = object_depths(maps["depth"], boxes, depth_std=maps.get("depth_std") if "depth_std" in asked else None, **self.readout)
+        return _ObjectsResult(*res, objects=objects, points=None if cloud is None else self.points_of(maps, *cloud))
 
 
 def _need_stats(want) -> bool:
@@ -282,13 +375,22 @@ class Predictor:
     tensors / None, an (xywh, counts) pair or a ``PaddedObjects``; independent of the objects the model's provider is fed -- is read out
     of the final map by one launch behind the finalize launch, and the result's ``objects`` ATTRIBUTE holds the ``ObjectDepths`` (None
     otherwise; ``PredictResult``'s fields are what they were).  The fp32 map is made for it even when ``want`` leaves "depth" out;
-    ``std_mean`` is filled when ``want`` names "depth_std"."""
+    ``std_mean`` is filled when ``want`` names "depth_std".
+    ``point_cloud``: None, or a dict with some of ``stride`` ((sy, sx) or one int), ``near`` / ``far`` (default the dataset's depth range),
+    ``min_confidence``, ``max_std``, ``capacity`` (rows per image, default the strided grid's size), ``colour`` (default True: the
+    frame's R, G, B in every record), ``pixel`` (default False: the y * W + x index of every point) -- the final map as compacted 3-D
+    points (objcavit_amd/point_cloud.py).  With it, ``intrinsics=`` of a call -- a [B, 4] tensor or a list of per-frame (fx, fy, cx, cy),
+    in pixels of the SOURCE frame: the predictor shifts the principal point by each frame's window origin -- is read by two launches
+    behind the finalize launch (and the object readout), and the result's ``points`` ATTRIBUTE holds the ``PointCloud`` (None
+    otherwise).  ``min_confidence > 0`` / a finite ``max_std`` make the "confidence" / "depth_std" maps for the filter (``bin_stats`` is
+    turned on) even when ``want`` leaves them out; byte 15 of a record is the confidence whenever that map is made, else 255.  Rows of
+    ``points.points`` at or beyond ``points.counts[b]`` are not written.  ``boxes`` and ``intrinsics`` are keyword arguments."""
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None,
-                 object_depth: Optional[dict] = None):
+                 point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -302,16 +404,17 @@ class Predictor:
 
     @torch.no_grad()
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",),
-                 boxes=None) -> PredictResult:
+                 intrinsics=None, boxes=None) -> PredictResult:
         want = _check_want(want)
-        if _need_stats(want):
+        if _need_stats(want) or (intrinsics is not None and _cloud_want(self.ends.cloud)):
             _turn_stats_on(self.model)
         frames = _frame_list(frames_u8, "frames_u8", 4)
         B = sum(int(f.shape[0]) for f in frames)
         size = self.ends.window_of(frames)
         out, mirror = self._forward(frames, B)
+        K = self.ends.intrinsics_on(intrinsics, frames[0].device, B)
         return self.ends.finish(out, mirror, size, self.ends.ground_truth(depth_gt, B), first_image_id, want,
-                                self.ends.boxes_on(boxes, frames[0].device, B))
+                                self.ends.boxes_on(boxes, frames[0].device, B), None if K is None else (K, frames))
 
 
 class PipelinedPredictor(_SlotPipeline):
@@ -323,7 +426,8 @@ class PipelinedPredictor(_SlotPipeline):
     tripped is ingested again from its kept frames for the re-run.  ``bin_edges`` of a result is
     None unless ``want`` names "bin_edges" (the graph's static tensor is then copied per step).  Wants ``GPU_MAX_HW_QUEUES`` >= slots
     set before the HIP runtime starts, like ``PipelinedValidation``.  ``object_depth`` / ``submit(..., boxes=)``: as ``Predictor``'s; the
-    readout runs on the slot's stream, a re-run step is read out from the re-run's map.
+    readout runs on the slot's stream, a re-run step is read out from the re-run's map.  ``point_cloud`` / ``submit(..., intrinsics=)``:
+    likewise; a list of differently sized frames gives one launch pair per frame.
 
         pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
         for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
@@ -336,13 +440,14 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
-                 crop: Optional[Tuple[int, int, int, int]] = None, object_depth: Optional[dict] = None):
+                 crop: Optional[Tuple[int, int, int, int]] = None, point_cloud: Optional[dict] = None,
+                 object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
-        if _need_stats(self.want):
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud)
+        if _need_stats(self.want) or _cloud_want(self.ends.cloud):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth)
         self.flip_tta = flip_tta
         ex = _frame_list(example_frames, "example_frames", 4)
         self.B = sum(int(f.shape[0]) for f in ex)
@@ -361,7 +466,7 @@ class PipelinedPredictor(_SlotPipeline):
     def _finish(self, out, step: _Step, first_image_id: int) -> PredictResult:
         gt = self.ends.ground_truth(step.depth_gt, self.B)
         out, mirror = _split(out, self.B) if self.flip_tta else (out, None)
-        res = self.ends.finish(out, mirror, self.size, gt, first_image_id, self.want, step.boxes)
+        res = self.ends.finish(out, mirror, self.size, gt, first_image_id, self.want, step.boxes, step.intrinsics)
         return res._replace(bin_edges=res.bin_edges.clone() if (self.want_edges and res.bin_edges is not None) else None)
 
     def collect(self) -> List[PredictResult]:
@@ -369,16 +474,26 @@ class PipelinedPredictor(_SlotPipeline):
         return self._collect()
 
     def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None,
-               boxes=None) -> None:
+               intrinsics=None, boxes=None) -> None:
         """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the readout boxes of the step's frames
-        (``object_depth`` keyword); lists are padded here, on the caller's stream, and the tensors are held like the frames."""
+        (``object_depth`` keyword); lists are padded here, on the caller's stream, and the tensors are held like the frames.
+        ``intrinsics``: the frames' (fx, fy, cx, cy) for the point cloud (``point_cloud`` keyword), uploaded here and held likewise;
+        the cloud's buffers are made per step on the slot's stream, its workspace is the slot's."""
         frames = _frame_list(frames_u8, "frames_u8", 4)
         if sum(int(f.shape[0]) for f in frames) != self.B or self.ends.window_of(frames) != self.size:
             raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")
         held = list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
         boxes = self.ends.boxes_on(boxes, frames[0].device, self.B)
         held += list(boxes or ())
-        self._submit(frames, held, _Step(depth_gt, boxes), first_image_id, (object_features, object_xywh_list))
+        K = self.ends.intrinsics_on(intrinsics, frames[0].device, self.B)
+        held += [] if K is None else [K]
+        self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames)), first_image_id,
+                     (object_features, object_xywh_list))
+        cloud = getattr(self._pending[-1].result, "points", None)
+        if cloud is not None:                                # made on the slot's stream, read by the caller on this one
+            for t in cloud:
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(t.device))
 
     def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
         """The record table [N * B, 10] ([N * B, 16] with ``loss``) of collected results that carried ground truth."""
