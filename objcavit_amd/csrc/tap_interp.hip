@@ -12,19 +12,32 @@
 // activation and writes fp32 and / or the hl32 split layout.  Exact re-association of the reference's arithmetic: the
 // interpolation uses ATen's coefficients (scale = (in - 1) / (out - 1), src = scale * dst, lambda = src - floor(src)).
 //
-// Work item: 4 output channels of 4 output pixels (rows Y, Y+2, Y+4, Y+6 of one column); a workgroup owns an 8 x 16 pixel
-// tile x 32 channels and walks the nine taps.  Per tap the 32-channel slab of the low-resolution pixels under the tile (its
-// footprint, < FQ pixels, 128 bytes each) is staged in LDS buffer (tap mod 3) by a FIFTH, producer wavefront with LDS-DMA
-// (global_load_lds_dwordx4: no registers, no ds_write), two taps ahead of the four consumer wavefronts.  The kernel is bound
-// by the latency of those ~10 KB pieces and by how much of it other workgroups on the CU can cover, not by HBM bandwidth
-// (ablations, tools/diag/tap_interp_diag.patch: interpolation alone 0.43 ms, staging + epilogue alone 0.55 ms, together
-// 0.80 ms when every wavefront did both through registers at two workgroups per CU): the producer / consumer split keeps the
-// consumers at 128 registers = 4 wavefronts per SIMD = THREE five-wavefront workgroups per CU (LDS: ~37 KB each for a 2x up-sampling; at
-// __launch_bounds__(320, 5) -- four workgroups -- the compiler spills 27 - 37 registers and the launch takes 1.9x as long, and removing the
-// kernel's LDS bank conflicts made it 9 % slower: profiles/r03_tap_interp_swizzle.txt).  The x interpolation
-// coefficients and LDS offsets depend on (pixel, dx) only and are formed once; the y ones per tap row.  The right-hand x
+// Work item (row form): 4 output channels of 4 CONSECUTIVE output rows of one column; a workgroup owns an 8 x 16 pixel tile x
+// 32 channels (two row blocks of 4) and walks the three tap rows dy.  The bilinear interpolation is separable and its x half
+// depends on (source row, X, dx) only, not on which output row asks: per tap row the consumers loop over the source rows r
+// their row block needs (4 at a 2x up-sampling, a run-time count), form
+//     u[r] = sum_dx wx0(X+dx) z_{3dy+dx}[r, x0(X+dx)] + wx1(X+dx) z_{3dy+dx}[r, x0(X+dx)+1]          (6 ds_read_b128, 6 FMAs per channel)
+// ONCE per row and add hy . u[r] to the accumulators of the pixels that use r as y0 or y1.  The rows of a block are the same
+// for every lane of a wavefront, so row indices and hy weights sit in scalar registers and the weight of pixel i for row r
+// (hy0, hy1 or 0) is selected on the scalar unit: 4 FMAs per channel per row whichever pixels use it.  That costs ~4 vector
+// instructions per row more than uniform branches around the FMAs would and measured 1 - 3 % FASTER than the branches
+// (profiles/tap_interp_rows.txt).  Against the per-tap form (a full 2-D bilinear per tap and pixel: 4 reads, 16 FMAs per 4
+// channels) the last stage issues 0.41x the LDS instructions and 0.74x the vector instructions, and the four bs-16 launches of
+// the benchmark take 1.36 ms instead of 1.65 ms.
+//
+// Staging: per tap row the 32-channel slabs of the low-resolution pixels under the tile (its footprint, < FQ pixels, 128 bytes
+// each) of the THREE taps dx are brought into LDS buffers 0..2 by a FIFTH, producer wavefront with LDS-DMA
+// (global_load_lds_dwordx4: no registers, no ds_write) and consumed together; the consumers hand the buffers back before the
+// next tap row is issued: five workgroup barriers per tile (ready x 3, free x 2) where the per-tap form had nine.  Nothing is
+// in flight while a tap row is consumed; the other workgroups of the CU cover it.  Six buffers with the next tap row streaming
+// in during the consumption (three barriers) measured the same where they fit beside each other (48 KB, footprint <= 63) and
+// 12 % slower on the first stage (72 KB, two workgroups per CU), so the three buffers stayed: 24 - 36 KB per workgroup, and at
+// 80 registers FOUR five-wavefront workgroups per CU.  (Round 3: removing the kernel's LDS bank conflicts made the per-tap form
+// 9 % slower, profiles/r03_tap_interp_swizzle.txt.)  A 16 x 16 tile with 8 rows per thread (footprint 1.56x its unique pixels
+// instead of 1.9x) measured 1 - 2 % slower on the four launches: tools/diag/tap_interp_tile16.patch.txt.
+// The x coefficients and LDS offsets depend on (pixel, dx) only and are formed once; the y ones per tap row.  The right-hand x
 // neighbour is always read at +128 bytes: where ATen clamps it (last column) its weight is exactly 0 and the slot read holds
-// staged (finite) data.
+// staged (finite) data.  On the last source row ATen's y1 = y0: y0 takes both shares and no second row is read.
 //
 // (Round 4 also formed the skip part INSIDE this launch, on the matrix cores: correct, tested, 8 % slower end to end -- a
 // wavefront-sized MFMA tile fed from L1 is what a GEMM with LDS tiles exists to avoid (profiles/r04_tap_skip.txt).  Removed in round
@@ -39,8 +52,9 @@ typedef __bf16 ti_bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 ti_h16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TY = 8, TX = 16, CB = 32;          // output tile and channel block
+constexpr int TR = TY / 2;                       // consecutive output rows per consumer thread (two row blocks per tile)
 constexpr int FQ = 192;                          // low-resolution pixels staged per tap (footprint capacity)
-constexpr int NBUF = 3;                          // LDS buffers: tap t lives in buffer t mod 3 (= dx)
+constexpr int NBUF = 3;                          // LDS buffers: tap 3 dy + dx lives in buffer dx
 
 struct TIArgs {
   const float* z;        // [B][h - 2 zpad][w - 2 zpad][9 Cout]: column t Cout + co = (Wa_t . x)[co]
@@ -67,7 +81,18 @@ __device__ __forceinline__ float ti_act(float v) {
 
 struct TIArgs;
 template <int ACT>
-__device__ __forceinline__ void ti_store(const TIArgs& p, const float4 (&acc)[4], const float4 (&sv)[4], int b, int Y0, int X, int n);
+__device__ __forceinline__ void ti_store(const TIArgs& p, const float4 (&acc)[TR], const float4 (&sv)[TR], int b, int Y, int X, int n);
+
+__device__ __forceinline__ void ti_fma4(float4& a, float w, const float4& v) {
+  a.x = fmaf(w, v.x, a.x); a.y = fmaf(w, v.y, a.y); a.z = fmaf(w, v.z, a.z); a.w = fmaf(w, v.w, a.w);
+}
+
+// a == b ? x : y on the scalar unit (the compiler's own select of two scalars that feed a vector instruction is a v_cndmask)
+__device__ __forceinline__ int ti_pick(int a, int b, int x, int y) {
+  int r;
+  asm("s_cmp_eq_u32 %1, %2\n\ts_cselect_b32 %0, %3, %4" : "=s"(r) : "s"(a), "s"(b), "s"(x), "s"(y) : "scc");
+  return r;
+}
 
 typedef __attribute__((address_space(1))) const void* ti_gptr;
 typedef __attribute__((address_space(3))) void* ti_lptr;
@@ -106,8 +131,7 @@ __global__ __launch_bounds__(320, 4) void tap_interp_kernel(TIArgs p) {
   if (tid >= 256) {
     // =========================== PRODUCER wavefront: LDS-DMA issuer ===========================
     // One instruction moves 64 chunks = 8 footprint pixels x 128 bytes to wave-uniform base + 16 lane; 4 NJ instructions
-    // per tap.  Three buffers, two taps ahead: in interval t (consumers on buffer t mod 3) tap t+2 is issued into the
-    // buffer read in interval t-1 and only tap t+1 -- issued a whole interval earlier -- is waited for (counted vmcnt).
+    // per tap, the three taps of a tap row dy together into the three buffers, once the consumers have handed them back.
     const int lane = tid & 63;
     const int hp = p.h - 2 * p.zpad, wp = p.w - 2 * p.zpad;           // the stored grid
     const int c4 = (lane & 7) * 4;
@@ -122,40 +146,40 @@ __global__ __launch_bounds__(320, 4) void tap_interp_kernel(TIArgs p) {
       const int qy = qy0 + q / fw - p.zpad, qx = qx0 + q % fw - p.zpad;
       soff[j] = (unsigned)qy < (unsigned)hp && (unsigned)qx < (unsigned)wp ? (qy * wp + qx) * 9 * p.Cout : -1;
     }
-    auto issue = [&](int t) {
-      __attribute__((address_space(3))) float* dst = (__attribute__((address_space(3))) float*)zs + (t % NBUF) * bufstride;
+    auto issue = [&](int dy) {
 #pragma unroll
-      for (int j = 0; j < 4 * NJ; ++j) {
-        const float* src = soff[j] >= 0 ? zb + soff[j] + t * p.Cout : zbr + t * p.Cout;
-        __builtin_amdgcn_global_load_lds((ti_gptr)src, (ti_lptr)(dst + j * 256), 16, 0, 0);
+      for (int dx = 0; dx < 3; ++dx) {
+        const int t = 3 * dy + dx;
+        __attribute__((address_space(3))) float* dst = (__attribute__((address_space(3))) float*)zs + dx * bufstride;
+#pragma unroll
+        for (int j = 0; j < 4 * NJ; ++j) {
+          const float* src = soff[j] >= 0 ? zb + soff[j] + t * p.Cout : zbr + t * p.Cout;
+          __builtin_amdgcn_global_load_lds((ti_gptr)src, (ti_lptr)(dst + j * 256), 16, 0, 0);
+        }
       }
     };
-    issue(0);
-    issue(1);
-    ti_wait_vm<4 * NJ>();
-    __builtin_amdgcn_s_barrier();
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      if (t + 2 < 9) {
-        issue(t + 2);
-        ti_wait_vm<4 * NJ>();                           // tap t+1 has landed, tap t+2 may stay in flight
-      } else {
-        ti_wait_vm<0>();
-      }
-      __builtin_amdgcn_s_barrier();
+    for (int dy = 0; dy < 3; ++dy) {
+      if (dy > 0) __builtin_amdgcn_s_barrier();         // the consumers have read tap row dy-1
+      issue(dy);
+      ti_wait_vm<0>();
+      __builtin_amdgcn_s_barrier();                     // tap row dy has landed
     }
     return;
   }
 
   // =========================== CONSUMERS ===========================
-  // items: channel group cg (4 channels) of pixels (Y0 + (tid >> 7) + 2 i, X0 + ((tid >> 3) & 15)), i = 0..3.
-  // Coefficients are zero where the tap falls outside the image (zero padding of the convolution).
+  // items: channel group cg (4 channels) of the TR consecutive pixels (Yb + i, X), i = 0..TR-1.  A wavefront holds 8 columns x
+  // 8 channel groups of ONE row block, so everything that depends on rows only is wave-uniform and kept in scalar registers.
+  // x coefficients are zero where the tap falls outside the image (zero padding of the convolution).
   const int cg = (tid & 7) * 4;
+  const int Xc = X0 + ((tid >> 3) & 15);
+  const int Yb = Y0 + TR * __builtin_amdgcn_readfirstlane(tid >> 7);
   int xo[3];                                                          // LDS float offset: buffer dx, column x0, channel group
   float wx0[3], wx1[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    const int X = X0 + ((tid >> 3) & 15) + d - 1;
+    const int X = Xc + d - 1;
     const bool ok = (unsigned)X < (unsigned)p.W;
     const float sx = p.sw * (ok ? X : 0);
     const int x0 = (int)sx;
@@ -165,80 +189,87 @@ __global__ __launch_bounds__(320, 4) void tap_interp_kernel(TIArgs p) {
     wx1[d] = ok ? w1 : 0.f;
   }
 
-  float4 acc[4], sv[4];                                // sv: the skip part of this item's pixels, requested before the taps
+  float4 acc[TR], sv[TR];                              // sv: the skip part of this item's pixels, requested before the taps
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int Y = Y0 + (tid >> 7) + 2 * i, X = X0 + ((tid >> 3) & 15);
-    const bool ok = p.s != nullptr && Y < p.H && X < p.W && cb0 + cg < p.Cout;
-    sv[i] = ok ? ld4(p.s + (((long)b * p.H + Y) * p.W + X) * p.Cout + cb0 + cg) : make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 0; i < TR; ++i) {
+    const int Y = Yb + i;
+    const bool ok = p.s != nullptr && Y < p.H && Xc < p.W && cb0 + cg < p.Cout;
+    sv[i] = ok ? ld4(p.s + (((long)b * p.H + Y) * p.W + Xc) * p.Cout + cb0 + cg) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 0; i < TR; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 
-  __builtin_amdgcn_s_barrier();                        // tap 0 is in LDS
-  asm volatile("" ::: "memory");
+  const int rowstride = fw * CB;
 #pragma unroll 1
   for (int dy = 0; dy < 3; ++dy) {
-    int iy0[4], iy1[4];
-    float hy0[4], hy1[4];
+    // the source rows of this block's output rows under tap row dy (scalar): pixel i takes hy0 of row ry0 and hy1 of row ry1;
+    // -1 = the tap row leaves the image.  Output rows are consecutive: at a y scale below 1 every row rlo..rhi is used by some
+    // pixel, at a larger one (accepted beside a strong x up-sampling) the rows in between get weight 0 from every pixel.
+    int ry0[TR], ry1[TR], hy0[TR], hy1[TR], rlo = 0, rhi = -1;      // hy: the weights' bits
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int Y = Y0 + (tid >> 7) + 2 * i + dy - 1;
+    for (int i = 0; i < TR; ++i) {
+      const int Y = Yb + i + dy - 1;
       const bool ok = (unsigned)Y < (unsigned)p.H;
       const float sy = p.sh * (ok ? Y : 0);
-      const int y0 = (int)sy, y1 = y0 + (y0 < p.h - 1 ? 1 : 0);
+      const int y0 = (int)sy;
+      const bool last = y0 >= p.h - 1;                                // last row: ATen's y1 = y0, so y0 takes both shares
       const float h1 = sy - (float)y0;
-      iy0[i] = ok ? (y0 - qy0) * fw * CB : 0;
-      iy1[i] = ok ? (y1 - qy0) * fw * CB : 0;
-      hy0[i] = ok ? 1.0f - h1 : 0.f;
-      hy1[i] = ok ? h1 : 0.f;
-    }
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {                   // tap 3 dy + dx lives in buffer dx
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float* r0p = zs + iy0[i] + xo[dx];
-        const float* r1p = zs + iy1[i] + xo[dx];
-        const float4 v00 = *reinterpret_cast<const float4*>(r0p);
-        const float4 v01 = *reinterpret_cast<const float4*>(r0p + CB);
-        const float4 v10 = *reinterpret_cast<const float4*>(r1p);
-        const float4 v11 = *reinterpret_cast<const float4*>(r1p + CB);
-        // four fused multiply-adds per channel INTO the accumulator (two channels per v_pk_fma_f32): the sum-then-add form cost
-        // a v_pk_mul + a v_pk_add more per channel pair, a fifth of the loop's vector instructions in a kernel whose consumers are
-        // bound by them (profiles/r05_sq.json: 1024 per wavefront item, vector pipe ~50 % busy beside HBM at ~55 %)
-        const float a = hy0[i] * wx0[dx], bq = hy0[i] * wx1[dx], c = hy1[i] * wx0[dx], d = hy1[i] * wx1[dx];
-        acc[i].x = fmaf(d, v11.x, fmaf(c, v10.x, fmaf(bq, v01.x, fmaf(a, v00.x, acc[i].x))));
-        acc[i].y = fmaf(d, v11.y, fmaf(c, v10.y, fmaf(bq, v01.y, fmaf(a, v00.y, acc[i].y))));
-        acc[i].z = fmaf(d, v11.z, fmaf(c, v10.z, fmaf(bq, v01.z, fmaf(a, v00.z, acc[i].z))));
-        acc[i].w = fmaf(d, v11.w, fmaf(c, v10.w, fmaf(bq, v01.w, fmaf(a, v00.w, acc[i].w))));
+      ry0[i] = __builtin_amdgcn_readfirstlane(ok ? y0 : -1);
+      ry1[i] = __builtin_amdgcn_readfirstlane(ok && !last ? y0 + 1 : -1);
+      hy0[i] = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, last ? (1.0f - h1) + h1 : 1.0f - h1));
+      hy1[i] = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, h1));
+      if (ok) {
+        if (rhi < 0) rlo = ry0[i];
+        rhi = max(ry0[i], ry1[i]);
       }
-      __builtin_amdgcn_sched_barrier(0);               // keep each tap's arithmetic with its LDS reads
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this tap's LDS reads are done before the buffer is handed back
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
     }
+    const float* rp = zs + (rlo - qy0) * rowstride;
+
+    __builtin_amdgcn_s_barrier();                      // tap row dy is in LDS
+    asm volatile("" ::: "memory");
+    for (int r = rlo; r <= rhi; ++r, rp += rowstride) {
+      // x interpolation of source row r under the three taps of this tap row: once per row, whichever output rows ask
+      float4 v[6];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        v[2 * d] = *reinterpret_cast<const float4*>(rp + xo[d]);
+        v[2 * d + 1] = *reinterpret_cast<const float4*>(rp + xo[d] + CB);
+      }
+      float4 u;
+      u.x = wx0[0] * v[0].x; u.y = wx0[0] * v[0].y; u.z = wx0[0] * v[0].z; u.w = wx0[0] * v[0].w;
+      ti_fma4(u, wx1[0], v[1]);
+#pragma unroll
+      for (int d = 1; d < 3; ++d) {
+        ti_fma4(u, wx0[d], v[2 * d]);
+        ti_fma4(u, wx1[d], v[2 * d + 1]);
+      }
+#pragma unroll
+      for (int i = 0; i < TR; ++i)                     // hy0, hy1 or 0: selected on the scalar unit
+        ti_fma4(acc[i], __builtin_bit_cast(float, ti_pick(r, ry0[i], hy0[i], ti_pick(r, ry1[i], hy1[i], 0))), u);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this tap row's LDS reads are done before its buffers are handed back
+    if (dy < 2) __builtin_amdgcn_s_barrier();
   }
 
   const int n = cb0 + cg;
   if (n >= p.Cout) return;
-  const int Yt = Y0 + (tid >> 7), X = X0 + ((tid >> 3) & 15);
   switch (p.act) {                                                    // uniform
-    case OCV_ACT_LEAKY_RELU: ti_store<OCV_ACT_LEAKY_RELU>(p, acc, sv, b, Yt, X, n); break;
-    case OCV_ACT_SILU: ti_store<OCV_ACT_SILU>(p, acc, sv, b, Yt, X, n); break;
-    case OCV_ACT_RELU: ti_store<OCV_ACT_RELU>(p, acc, sv, b, Yt, X, n); break;
-    default: ti_store<OCV_ACT_NONE>(p, acc, sv, b, Yt, X, n); break;
+    case OCV_ACT_LEAKY_RELU: ti_store<OCV_ACT_LEAKY_RELU>(p, acc, sv, b, Yb, Xc, n); break;
+    case OCV_ACT_SILU: ti_store<OCV_ACT_SILU>(p, acc, sv, b, Yb, Xc, n); break;
+    case OCV_ACT_RELU: ti_store<OCV_ACT_RELU>(p, acc, sv, b, Yb, Xc, n); break;
+    default: ti_store<OCV_ACT_NONE>(p, acc, sv, b, Yb, Xc, n); break;
   }
 }
 
-// + skip part + bias, activation, fp32 and / or hl32 split store of one item's four pixels (rows Y, Y+2, Y+4, Y+6)
+// + skip part + bias, activation, fp32 and / or hl32 split store of one item's TR pixels (rows Y .. Y + TR - 1)
 template <int ACT>
-__device__ __forceinline__ void ti_store(const TIArgs& p, const float4 (&acc)[4], const float4 (&sv)[4], int b, int Y, int X, int n) {
+__device__ __forceinline__ void ti_store(const TIArgs& p, const float4 (&acc)[TR], const float4 (&sv)[TR], int b, int Y, int X, int n) {
   if (X >= p.W) return;
   const float4 bv = p.bias != nullptr ? ld4(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (Y + 2 * i >= p.H) break;
-    const long pix = ((long)b * p.H + Y + 2 * i) * p.W + X;
+  for (int i = 0; i < TR; ++i) {
+    if (Y + i >= p.H) break;
+    const long pix = ((long)b * p.H + Y + i) * p.W + X;
     float4 v = acc[i];
     v.x += sv[i].x; v.y += sv[i].y; v.z += sv[i].z; v.w += sv[i].w;
     v.x = ti_act<ACT>(v.x + bv.x); v.y = ti_act<ACT>(v.y + bv.y);
@@ -296,6 +327,9 @@ extern "C" int ocv_tap_interp_supported(int h, int w, int H, int W, int Cout) {
   return ti_footprint(h, w, H, W) < FQ ? 1 : 0;                     // + the one spare slot the right-hand neighbour may touch
 }
 
+// 256-chunk staging rounds per TAP (ti_launch's nj: the kernel template's NJ, and the size of one LDS buffer in 4 KB units).
+// The kernel stages the three taps of a tap row together, 3 x this number per barrier interval; callers that rank shapes by
+// it (the Python routing, the decoder-stage tests) still get the per-tap figure.
 extern "C" int ocv_tap_interp_staging_rounds(int h, int w, int H, int W) {
   if (h < 1 || w < 1 || H < 1 || W < 1) return 0;
   return ocv_cdiv(ti_footprint(h, w, H, W) + 1, 32);                // (ti_launch's nj)
@@ -335,22 +369,18 @@ int ti_launch(const char* who, const float* z, int h, int w, int zpad, const flo
     if (zrc != 0) return zrc;
   }
   const dim3 grid((unsigned)nwg, ocv_cdiv(Cout, CB));
-  const size_t buf = (size_t)a.fq_cap * CB * sizeof(float);
-  const size_t lds = NBUF * buf;
-  const void* fn = nullptr;
+  const size_t lds = NBUF * (size_t)a.fq_cap * CB * sizeof(float);
   switch (nj) {
-#define OCV_TI_CASE(NJ) case NJ: fn = reinterpret_cast<const void*>(&tap_interp_kernel<NJ>); \
-    hipLaunchKernelGGL((tap_interp_kernel<NJ>), grid, dim3(320), lds, (hipStream_t)stream, a); break;
+#define OCV_TI_CASE(NJ) case NJ: hipLaunchKernelGGL((tap_interp_kernel<NJ>), grid, dim3(320), lds, (hipStream_t)stream, a); break;
     OCV_TI_CASE(1) OCV_TI_CASE(2) OCV_TI_CASE(3) OCV_TI_CASE(4) OCV_TI_CASE(5)
 #undef OCV_TI_CASE
     default: {                                                      // nj == 6: 72 KB of dynamic LDS, above the 64 KB default limit
-      fn = reinterpret_cast<const void*>(&tap_interp_kernel<6>);
-      const hipError_t attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tap_interp_kernel<6>),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       OCV_CHECK_ARG(attr == hipSuccess, "%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(attr));
       hipLaunchKernelGGL((tap_interp_kernel<6>), grid, dim3(320), lds, (hipStream_t)stream, a);
     }
   }
-  (void)fn;
   OCV_CHECK_LAUNCH(who);
   return 0;
 }
