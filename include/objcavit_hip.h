@@ -740,6 +740,39 @@ int ocv_depth_unproject_fwd(const float* depth, const float* K, const float* con
                             long frame_stride, long row_stride, int Hs, int Ws, int top, int left, int B, int H, int W, int sy, int sx,
                             float near, float far, float min_confidence, float max_std, int cap, float* points, int* pixel, int* counts,
                             int* total, void* workspace, size_t workspace_bytes, ocv_stream_t stream);
+/* Depth ERROR per detection box, and over objects against background: the validation metrics of ocv_depth_metrics_fwd, segmented by the
+ * boxes of ocv_object_depth_fwd (no counterpart in the reference; the statement the tests compare against is tests/object_metrics_ref.py).
+ * pred, pred_mirror (nullable, still mirrored), h, w, gt, H, W, min_depth, max_depth and the crop box: exactly as ocv_depth_metrics_fwd
+ * takes them; the per-pixel value v (clamp that keeps NaN, un-mirrored average, bilinear align_corners taps with the identity short-cut
+ * at equal sizes, nan -> min_depth, +-inf -> max_depth) and the VALID pixels (min_depth < gt <= max_depth inside the crop box) are that
+ * entry point's.  xywh, xywh_row_stride, counts, cap, half: exactly as ocv_object_depth_fwd takes them, in pixels of the ground truth's
+ * H x W grid; a box's pixels are that entry point's rule.  A box OWNS its pixels that are valid.
+ * One record = 10 floats over a set of owned pixels:
+ *   0 abs_rel  1 sq_rel  2 rmse  3 rmse_log  4 log10  5 delta1  6 delta2  7 delta3     the eight means of ocv_depth_metrics_fwd's record
+ *                                                                                      (float64 sums, the two RMSEs square-rooted)
+ *   8 n_valid  the number of pixels in the set (exact below 2^24)
+ *   9 gt_mean  the float64 mean of gt over the set, rounded to fp32
+ * All ten are 0 for an empty set: n_valid = 0 is the flag.
+ * boxes_out [B][cap][10]: row r of image b = the record of box r; overlapping boxes each count their own pixels; a row at or beyond
+ *   counts[b], an empty box (outside the map, of no size, non-finite, the <UNK> box -1, -1, -1, -1) and a box without a valid pixel
+ *   are all zero.  Every element is written.
+ * regions_out [B][2][10], or null to skip the region pass: row 0 = the record over the valid pixels under ANY of the image's first
+ *   min(counts[b], cap) boxes (a pixel under several counts once), row 1 = over the valid pixels under none.  Their n_valid add up to
+ *   the image's n_valid of ocv_depth_metrics_fwd exactly; the n-weighted recombination of the two rows (RMSEs through their squares) is
+ *   that image's record.  The region pass takes cap <= OCV_OBJECT_METRICS_MAX_BOXES; the box pass has no such bound.
+ * workspace: ocv_object_metrics_workspace_bytes (0 for sizes the entry point refuses), 8-byte aligned; read and written by the region
+ * pass only (null / 0 with regions_out = null).
+ * One launch of B * cap workgroups for the boxes, two for the regions ((tiles, B) partials, then B finishes); gt is read over the boxes
+ * and once more over the map; no allocation, no synchronisation, counts read on the device only (capturable); sums in float64 in a fixed
+ * order, the counts as integers, no float atomics: two calls give identical bytes.
+ * -1 with a message before any launch on: a null required pointer, bad sizes, min_depth >= max_depth, a crop box outside the map, half
+ * outside (0, 0.5], xywh_row_stride < 4, cap above the bound with regions_out given, misaligned pointers, a workspace that is too small. */
+#define OCV_OBJECT_METRICS_MAX_BOXES 1024
+size_t ocv_object_metrics_workspace_bytes(int B, int H, int W);
+int ocv_object_metrics_fwd(const float* pred, const float* pred_mirror, int h, int w, const float* gt, int H, int W, float min_depth,
+                           float max_depth, int crop_y0, int crop_y1, int crop_x0, int crop_x1, const float* xywh, long xywh_row_stride,
+                           const int* counts, int B, int cap, float half, float* boxes_out, float* regions_out, void* workspace,
+                           size_t workspace_bytes, ocv_stream_t stream);
 
 /* Tail of mViT / ObjCAViT.forward + glue of AdaBins / GraphBins.forward in one launch (modules/miniViT.py:33-42, modules/AdaBins.py:79-83):
  *   y = raw [B][n_bins] (the regressor's last Linear) -> OCV_BINNORM_LINEAR: relu(y) + 0.1 | OCV_BINNORM_SIGMOID: sigmoid(y) |

@@ -130,6 +130,9 @@ PROTOTYPES = {
                                                _stream]),
     "ocv_object_depth_fwd": (C.c_int, [_f32p, _f32p, _f32p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                        C.POINTER(C.c_double), C.c_int, _f32p, _stream]),
+    "ocv_object_metrics_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ocv_object_metrics_fwd": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_float, C.c_float] + [C.c_int] * 4 +
+                               [_f32p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_float, _f32p, _f32p, C.c_void_p, C.c_size_t, _stream]),
     "ocv_depth_unproject_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "ocv_depth_unproject_fwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _u8p, C.c_long, C.c_long] + [C.c_int] * 9 + [C.c_float] * 4 +
                                 [C.c_int, _f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _stream]),

@@ -13,20 +13,21 @@
 // Two stages, fixed order, no float atomics: (tiles, B) workgroups reduce 9 double-precision sums each, a second tiny
 // launch adds the tiles in order and finishes the means / square roots.  HBM-bound: 4 B of ground truth per pixel.
 #include "common.hpp"
+#include "metric_pixel.hpp"
 #include "../../include/objcavit_hip.h"
 
 namespace {
 
-constexpr int NSUM = 9;           // abs_rel, sq_rel, sq, sq_log, log10, d1, d2, d3, count
+using namespace ocv_metric;       // NSUM, MapView, the per-pixel statement, record, metric_tiles (shared with csrc/object_metrics.hip)
+
 constexpr int NLOSS = 4;          // sum g, sum g^2 (g = log p - log gt), sum_t min_k (t - c_k)^2, masked count
 constexpr int MAX_BINS = 1024;
 constexpr unsigned NO_TARGET_LO = 0xFFFFFFFFu, NO_TARGET_HI = 0u;   // empty interval: above / below every valid target's bit pattern
 
-struct MetArgs {
+struct MetArgs : MapView {
   const float *pred, *mirror, *gt;
   double* part;                   // [B][tiles][NSUM]
-  int h, w, H, W, y0, y1, x0, x1, tiles;
-  float sh, sw, dmin, dmax;
+  int y0, y1, x0, x1, tiles;
 };
 
 // The validation loss rides on the same pass (ocv_depth_metrics_loss_fwd: losses/SILogLoss.py:28-56, losses/BinsChamferLoss.py:21-37).
@@ -36,15 +37,6 @@ struct LossArgs {
   unsigned* slab;                 // [B][tiles][2][n_bins + 1]: smallest / largest target per interval between sorted centres
   int n_bins;
 };
-
-// torch.clamp semantics: NaN stays NaN (fminf / fmaxf would drop it)
-__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
-
-__device__ __forceinline__ float tap(const MetArgs& p, const float* pb, const float* mb, int y, int x) {
-  const float a = clamp_keep_nan(pb[y * p.w + x], p.dmin, p.dmax);
-  if (mb == nullptr) return a;
-  return 0.5f * (a + clamp_keep_nan(mb[y * p.w + (p.w - 1 - x)], p.dmin, p.dmax));
-}
 
 // Bin centres 0.5 (e[k+1] + e[k]) of one image, sorted ascending into `cen` (rank sort: every thread counts the centres below its
 // own, ties by index; all lanes read the same LDS word per step).  The edges may come in any order: a scanned cumsum is not
@@ -121,17 +113,7 @@ __global__ __launch_bounds__(256) void depth_metrics_partial_kernel(MetArgs p, L
     const bool mask = g > p.dmin && g <= p.dmax;
     const bool valid = mask && Y >= p.y0 && Y < p.y1 && X >= p.x0 && X < p.x1;
     if (LOSS ? mask : valid) {
-      // ATen upsample_bilinear2d, align_corners = True
-      const float sy = p.sh * Y, sx = p.sw * X;
-      const int ya = (int)sy, xa = (int)sx;
-      const int yb = ya + (ya < p.h - 1 ? 1 : 0), xb = xa + (xa < p.w - 1 ? 1 : 0);
-      const float h1 = sy - (float)ya, h0 = 1.0f - h1, w1 = sx - (float)xa, w0 = 1.0f - w1;
-      // (all four terms always, so a NaN tap reaches its neighbours through a zero weight exactly as in ATen; equal
-      // sizes are ATen's identity short-cut, where it does not)
-      float v = (p.h == p.H && p.w == p.W)
-                    ? tap(p, pb, mb, Y, X)
-                    : h0 * (w0 * tap(p, pb, mb, ya, xa) + w1 * tap(p, pb, mb, ya, xb)) +
-                          h1 * (w0 * tap(p, pb, mb, yb, xa) + w1 * tap(p, pb, mb, yb, xb));
+      float v = resized(p, pb, mb, Y, X);
       if constexpr (LOSS) {
         const float gl = logf(v) - logf(g);                       // a NaN prediction stays NaN here, as in the reference
         lacc[0] += (double)gl;
@@ -149,19 +131,11 @@ __global__ __launch_bounds__(256) void depth_metrics_partial_kernel(MetArgs p, L
         if (bits > thi[j]) atomicMax(&thi[j], bits);
       }
       if (LOSS && !valid) continue;
-      if (v != v) v = p.dmin;                                   // nan_to_num(nan = min, posinf = neginf = max)
-      else if (__builtin_isinf(v)) v = p.dmax;
-      const float d = g - v, ratio = fmaxf(g / v, v / g);
-      const float dl = logf(g) - logf(v);
-      s[0] += fabsf(d) / g;
-      s[1] += d * d / g;
-      s[2] += d * d;
-      s[3] += dl * dl;
-      s[4] += fabsf(log10f(g) - log10f(v));
-      s[5] += ratio < 1.25f ? 1.f : 0.f;
-      s[6] += ratio < 1.25f * 1.25f ? 1.f : 0.f;
-      s[7] += ratio < 1.25f * 1.25f * 1.25f ? 1.f : 0.f;
-      s[8] += 1.f;
+      v = fixed(p, v);
+      float t[NSUM];
+      terms(g, v, t);
+#pragma unroll
+      for (int i = 0; i < NSUM; ++i) s[i] += t[i];
       if (++pending == 64) {                                    // short fp32 runs, double-precision totals
 #pragma unroll
         for (int i = 0; i < NSUM; ++i) { acc[i] += (double)s[i]; s[i] = 0.f; }
@@ -209,17 +183,8 @@ __global__ __launch_bounds__(64 * NSUM) void depth_metrics_finish_kernel(const d
   if (lane == 0) tot[i] = s;
   __syncthreads();
   if (threadIdx.x != 0) return;
-  const double n = tot[8] > 0.0 ? tot[8] : 1.0;
   float* r = rec + (long)b * 10;
-  r[0] = (float)(tot[0] / n);
-  r[1] = (float)(tot[1] / n);
-  r[2] = (float)sqrt(tot[2] / n);
-  r[3] = (float)sqrt(tot[3] / n);
-  r[4] = (float)(tot[4] / n);
-  r[5] = (float)(tot[5] / n);
-  r[6] = (float)(tot[6] / n);
-  r[7] = (float)(tot[7] / n);
-  r[8] = (float)tot[8];
+  record(tot, r);
   r[9] = (float)(first_id + b);
 }
 
@@ -297,13 +262,6 @@ __global__ __launch_bounds__(1024) void val_loss_finish_kernel(LossArgs q, int t
   r[5] = (float)(first_id + b);
 }
 
-int metric_tiles(int B, long P) {
-  long t = (2048 + B - 1) / B;                         // ~2048 workgroups per launch
-  const long maxt = (P + 4095) / 4096;                 // at least 16 pixels per thread
-  if (t > maxt) t = maxt;
-  return (int)(t < 1 ? 1 : t);
-}
-
 }  // namespace
 
 extern "C" size_t ocv_depth_metrics_workspace_bytes(int B, int H, int W) {
@@ -323,8 +281,7 @@ extern "C" int ocv_depth_metrics_fwd(const float* pred, const float* pred_mirror
   OCV_CHECK_ARG(workspace_bytes >= ocv_depth_metrics_workspace_bytes(B, H, W) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                 "ocv_depth_metrics_fwd: workspace too small or misaligned");
   const int tiles = metric_tiles(B, (long)H * W);
-  MetArgs a{pred, pred_mirror, gt, (double*)workspace, h, w, H, W, crop_y0, crop_y1, crop_x0, crop_x1, tiles,
-            H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f, min_depth, max_depth};
+  MetArgs a{map_view(h, w, H, W, min_depth, max_depth), pred, pred_mirror, gt, (double*)workspace, crop_y0, crop_y1, crop_x0, crop_x1, tiles};
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(depth_metrics_partial_kernel<false>, dim3(tiles, B), dim3(256), 0, st, a, LossArgs{nullptr, nullptr, nullptr, 0});
   OCV_CHECK_LAUNCH("ocv_depth_metrics_fwd(partial)");
@@ -357,8 +314,7 @@ extern "C" int ocv_depth_metrics_loss_fwd(const float* pred, const float* pred_m
   const int tiles = metric_tiles(B, (long)H * W);
   const size_t wg = (size_t)B * tiles;
   double* part = (double*)workspace;
-  MetArgs a{pred, pred_mirror, gt, part, h, w, H, W, crop_y0, crop_y1, crop_x0, crop_x1, tiles,
-            H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f, min_depth, max_depth};
+  MetArgs a{map_view(h, w, H, W, min_depth, max_depth), pred, pred_mirror, gt, part, crop_y0, crop_y1, crop_x0, crop_x1, tiles};
   LossArgs q{bin_edges, part + wg * NSUM, (unsigned*)(part + wg * (NSUM + NLOSS)), n_bins};
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(depth_metrics_partial_kernel<true>, dim3(tiles, B), dim3(256), 0, st, a, q);

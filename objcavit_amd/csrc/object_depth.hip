@@ -15,11 +15,9 @@
 // so most lanes of a wave hit ONE bin: the two most common digits of a wave are counted with a ballot and added once by a leader lane,
 // only the rest add per lane.  The sums run in a fixed order -- per-thread partials over the thread's fixed pixels, xor shuffles, the
 // waves' partials from LDS in wave order -- so two calls are bit-equal; there is no float atomic.
+#include "box_edges.hpp"
 #include "common.hpp"
 #include "../../include/objcavit_hip.h"
-
-#include <float.h>
-#include <math.h>
 
 namespace {
 
@@ -40,20 +38,6 @@ __device__ __forceinline__ unsigned od_key(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float od_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// [lo, hi) of the pixels whose centre lies in [c - half * size, c + half * size): every statement rounded to fp32 on its own (the
-// library is built with contraction on: a fused half * size would move an edge by a pixel against the plain statement)
-__device__ __forceinline__ bool od_edges(float c, float size, float half, int limit, int& lo, int& hi) {
-  const float hs = __fmul_rn(half, size);
-  float a = ceilf(__fsub_rn(__fsub_rn(c, hs), 0.5f));
-  float b = ceilf(__fsub_rn(__fadd_rn(c, hs), 0.5f));
-  if (!(fabsf(a) <= FLT_MAX) || !(fabsf(b) <= FLT_MAX)) return false;      // NaN or inf
-  a = fminf(fmaxf(a, 0.f), (float)limit);
-  b = fminf(fmaxf(b, 0.f), (float)limit);
-  lo = (int)a;
-  hi = (int)b;
-  return hi > lo;
-}
 
 // ++hist[digit] for the lanes with `on`, called by a whole wave: two rounds of "the first such lane's digit, counted by ballot, added
 // once", then one atomic per lane that is left

@@ -1,6 +1,6 @@
 """hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip), full-resolution depth
-maps out (csrc/depth_finalize.hip), and what is read out of the final map behind them: per-box statistics (csrc/object_depth.hip) and the
-point cloud (csrc/point_cloud.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
+maps out (csrc/depth_finalize.hip), and what is read out of the final map behind them: per-box statistics (csrc/object_depth.hip), the
+point cloud (csrc/point_cloud.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
 static input)."""
 from __future__ import annotations
@@ -242,6 +242,64 @@ def object_depth(depth: torch.Tensor, xywh: torch.Tensor, counts: torch.Tensor, 
     return out
 
 
+OBJECT_METRICS_COLUMNS = 10       # abs_rel, sq_rel, rmse, rmse_log, log10, delta1, delta2, delta3, n_valid, gt_mean
+OBJECT_METRICS_MAX_BOXES = 1024   # include/objcavit_hip.h: OCV_OBJECT_METRICS_MAX_BOXES, boxes per image the region pass takes
+
+
+def object_metrics(pred: torch.Tensor, gt: torch.Tensor, xywh: torch.Tensor, counts: torch.Tensor, min_depth: float, max_depth: float,
+                   crop: Optional[Tuple[int, int, int, int]] = None, pred_mirror: Optional[torch.Tensor] = None, shrink: float = 1.0,
+                   regions: bool = True, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Depth error per detection box and over objects against background: ``pred`` [B, 1, h, w], ``gt`` [B, 1, H, W], depth range,
+    ``crop`` = (y0, y1, x0, x1) and ``pred_mirror`` as ``depth_metrics`` takes them; ``xywh`` fp32 [B, cap, k >= 4] (rows may be strided),
+    ``counts`` int32 [B] on the device and ``shrink`` as ``object_depth`` takes them, in pixels of the ground truth's grid ->
+    (boxes fp32 [B, cap, 10], regions fp32 [B, 2, 10] or None without ``regions``).  A record is the eight metrics of ``depth_metrics``
+    over a set of valid pixels, then n_valid and the float64 mean of gt: per box over the box's valid pixels (all zero for rows at or
+    beyond ``counts[b]``, empty boxes and boxes without a valid pixel), regions[:, 0] over the valid pixels under any of the image's
+    boxes, regions[:, 1] over those under none -- their n_valid add up to ``depth_metrics``' exactly.  ``out``: a [B, cap, 10] table to
+    write the boxes into.  One launch for the boxes, two for the regions (ocv_object_metrics_fwd), the counts are read on the device
+    only; with ``regions`` at most ``OBJECT_METRICS_MAX_BOXES`` rows per image."""
+    lib = _lib.load()
+    _req(pred, "pred"); _req(gt, "gt")
+    if pred.dim() != 4 or gt.dim() != 4 or pred.shape[1] != 1 or gt.shape[1] != 1 or pred.shape[0] != gt.shape[0]:
+        raise ValueError("object_metrics: expected pred [B,1,h,w] and gt [B,1,H,W]")
+    if pred_mirror is not None:
+        _req(pred_mirror, "pred_mirror")
+        if pred_mirror.shape != pred.shape:
+            raise ValueError("object_metrics: pred_mirror must have pred's shape")
+    B, _, h, w = (int(v) for v in pred.shape)
+    H, W = (int(v) for v in gt.shape[2:])
+    _req(xywh, "xywh", contiguous=False)
+    if xywh.dim() != 3 or xywh.shape[0] != B or xywh.shape[1] < 1 or xywh.shape[2] < 4:
+        raise ValueError(f"object_metrics: expected xywh [{B}, cap >= 1, k >= 4], got {tuple(xywh.shape)}")
+    cap = int(xywh.shape[1])
+    st = xywh.stride()
+    row = int(st[1]) if cap > 1 else max(int(st[1]), 4)
+    if st[2] != 1 or row < 4 or (B > 1 and st[0] != cap * row):
+        raise ValueError(f"object_metrics: xywh rows must be dense and evenly spaced over the batch (strides {st})")
+    _req(counts, "counts", torch.int32)
+    if tuple(counts.shape) != (B,):
+        raise ValueError(f"object_metrics: counts must be int32 [{B}], got {tuple(counts.shape)}")
+    shrink = float(shrink)
+    if not 0.0 < shrink <= 1.0 or C.c_float(0.5 * shrink).value <= 0.0:
+        raise ValueError(f"object_metrics: shrink must be in (0, 1], got {shrink}")
+    if regions and cap > OBJECT_METRICS_MAX_BOXES:
+        raise ValueError(f"object_metrics: {cap} box rows per image; the region pass takes at most {OBJECT_METRICS_MAX_BOXES} "
+                         "(regions=False gives the boxes alone)")
+    y0, y1, x0, x1 = crop if crop is not None else (0, H, 0, W)
+    out = _out_slice(out, (B, cap, OBJECT_METRICS_COLUMNS), torch.float32, pred.device, "object_metrics")
+    reg = ws = None
+    if regions:
+        from ._core import workspace as _workspace
+        reg = torch.empty((B, 2, OBJECT_METRICS_COLUMNS), dtype=torch.float32, device=pred.device)
+        ws = _workspace(int(lib.ocv_object_metrics_workspace_bytes(B, H, W)), pred.device, "object_metrics")
+    with timed("object_metrics"):
+        check(lib.ocv_object_metrics_fwd(pred.data_ptr(), _ptr(pred_mirror), h, w, gt.data_ptr(), H, W, float(min_depth), float(max_depth),
+                                         int(y0), int(y1), int(x0), int(x1), xywh.data_ptr(), row, counts.data_ptr(), B, cap,
+                                         0.5 * shrink, out.data_ptr(), _ptr(reg), _ptr(ws), 0 if ws is None else int(ws.numel()),
+                                         _stream()), "ocv_object_metrics_fwd")
+    return out, reg
+
+
 UNPROJECT_TILE = 2048             # include/objcavit_hip.h: OCV_UNPROJECT_TILE, candidates of the strided grid per workgroup
 
 
@@ -333,5 +391,6 @@ def depth_unproject(depth: torch.Tensor, K: torch.Tensor, capacity: int, stride:
     return res
 
 
-__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "depth_unproject",
+__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics",
+           "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
            "unproject_grid", "UNPROJECT_TILE"]

@@ -21,6 +21,7 @@ import torch
 from . import hip_ops
 from ._lib import HipLibraryError
 from .object_depth import DEFAULT_QUANTILES, ObjectDepths, object_depths, pad_boxes
+from .object_metrics import ObjectMetrics, object_metrics as _object_metrics
 from .point_cloud import PointCloud
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
@@ -35,20 +36,24 @@ PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "reco
                            defaults=(None, None))
 PredictResult.objects = None                   # the per-object readout (an ``ObjectDepths``) or None: an ATTRIBUTE, not a field
 PredictResult.points = None                    # the point cloud (a ``PointCloud``) or None: an attribute as well
+PredictResult.object_metrics = None            # the depth error per box / region (an ``ObjectMetrics``) or None: an attribute as well
 
 
 class _ObjectsResult(PredictResult):
-    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` attributes hold the step's ``ObjectDepths`` /
-    ``PointCloud``."""
+    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` / ``object_metrics`` attributes hold the step's
+    ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics``."""
 
-    def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, points: Optional[PointCloud] = None, **kw):
+    def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, points: Optional[PointCloud] = None,
+                object_metrics: Optional[ObjectMetrics] = None, **kw):
         self = super().__new__(cls, *fields, **kw)
         self.objects = objects
         self.points = points
+        self.object_metrics = object_metrics
         return self
 
     def _replace(self, **kw):
-        return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects, points=self.points)
+        return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects, points=self.points,
+                              object_metrics=self.object_metrics)
 
 
 # what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth, its readout
@@ -104,6 +109,17 @@ def _readout_options(object_depth) -> Optional[dict]:
     if bad:
         raise ValueError(f"object_depth: unknown option(s) {sorted(bad)}; expected some of 'quantiles', 'shrink'")
     return {"quantiles": tuple(opts.get("quantiles", DEFAULT_QUANTILES)), "shrink": float(opts.get("shrink", 1.0))}
+
+
+def _metric_options(object_metrics) -> Optional[dict]:
+    """The ``object_metrics`` keyword of both predictors: None (no per-object error) or a dict with some of ``shrink`` / ``regions``."""
+    if object_metrics is None:
+        return None
+    opts = dict(object_metrics)
+    bad = set(opts) - {"shrink", "regions"}
+    if bad:
+        raise ValueError(f"object_metrics: unknown option(s) {sorted(bad)}; expected some of 'shrink', 'regions'")
+    return {"shrink": float(opts.get("shrink", 1.0)), "regions": bool(opts.get("regions", True))}
 
 
 _CLOUD_KEYS = ("stride", "near", "far", "min_confidence", "max_std", "capacity", "colour", "pixel")
@@ -170,9 +186,11 @@ def _frame_list(frames: Frames, what: str, dims: int) -> List[torch.Tensor]:
 class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
-    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None):
+    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None,
+                 object_metrics=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.readout = _readout_options(object_depth)
+        self.errors = _metric_options(object_metrics)
         self.min_depth, self.max_depth = _depth_range(args)
         self.cloud = _cloud_options(point_cloud, self.min_depth, self.max_depth)
         self.vmin = self.min_depth if vmin is None else float(vmin)
@@ -240,8 +258,9 @@ class _Ends:
         return out
 
     def boxes_on(self, boxes, device, B: int):
-        """The readout boxes of a step as (xywh, counts) on the device, or None without the ``object_depth`` keyword / without boxes."""
-        if self.readout is None or boxes is None:
+        """The boxes of a step as (xywh, counts) on the device, or None without boxes / with neither the ``object_depth`` nor the
+        ``object_metrics`` keyword."""
+        if (self.readout is None and self.errors is None) or boxes is None:
             return None
         xywh, counts = pad_boxes(boxes, device)
         if xywh.dim() != 3 or int(xywh.shape[0]) != B or tuple(counts.shape) != (B,):
@@ -296,10 +315,14 @@ class _Ends:
                want: Tuple[str, ...], boxes=None, cloud=None) -> PredictResult:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
         the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  ``boxes``
-        (``boxes_on``'s pair): the per-object readout right behind the final map, which is then made even if ``want`` leaves it out.
+        (``boxes_on``'s pair): with the ``object_depth`` keyword the per-object readout right behind the final map, which is then made
+        even if ``want`` leaves it out; with the ``object_metrics`` keyword and ground truth the per-object error right behind the metric
+        launch, from the tensors that launch reads.
         ``cloud`` = (K of the source frames [B, 4], the frames): the point cloud behind the map (and behind the readout), with the
         maps its filters read made likewise."""
         asked = want
+        errors = boxes if (self.errors is not None and depth_gt is not None) else None
+        boxes = boxes if self.readout is not None else None
         if (boxes is not None or cloud is not None) and "depth" not in want:
             want = want + ("depth",)
         if cloud is not None:
@@ -318,15 +341,16 @@ class _Ends:
         rec = None
         if depth_gt is not None:
             rec = _records(pred, mirror_pred, edges, depth_gt, self.args, self.min_depth, self.max_depth, first_image_id, self.loss)
+        table = None if errors is None else _object_metrics(pred, depth_gt, errors, self.args, pred_mirror=mirror_pred, **self.errors)
         res = PredictResult(maps.get("depth") if "depth" in asked else None, maps.get("depth_u16"), maps.get("rgb8"), rec, edges,
                             maps.get("depth_std") if "depth_std" in asked else None,
                             maps.get("confidence") if "confidence" in asked else None)
-        if boxes is None and cloud is None:
+        if boxes is None and cloud is None and table is None:
             return res
         objects = None
         if boxes is not None:
             objects = object_depths(maps["depth"], boxes, depth_std=maps.get("depth_std") if "depth_std" in asked else None, **self.readout)
-        return _ObjectsResult(*res, objects=objects, points=None if cloud is None else self.points_of(maps, *cloud))
+        return _ObjectsResult(*res, objects=objects, points=None if cloud is None else self.points_of(maps, *cloud), object_metrics=table)
 
 
 def _need_stats(want) -> bool:
@@ -384,13 +408,18 @@ class Predictor:
     behind the finalize launch (and the object readout), and the result's ``points`` ATTRIBUTE holds the ``PointCloud`` (None
     otherwise).  ``min_confidence > 0`` / a finite ``max_std`` make the "confidence" / "depth_std" maps for the filter (``bin_stats`` is
     turned on) even when ``want`` leaves them out; byte 15 of a record is the confidence whenever that map is made, else 255.  Rows of
-    ``points.points`` at or beyond ``points.counts[b]`` are not written.  ``boxes`` and ``intrinsics`` are keyword arguments."""
+    ``points.points`` at or beyond ``points.counts[b]`` are not written.  ``boxes`` and ``intrinsics`` are keyword arguments.
+    ``object_metrics``: None, or a dict with some of ``shrink`` / ``regions`` -- the depth error per box and over objects against
+    background (objcavit_amd/object_metrics.py).  With it, a call that has both ``depth_gt`` and ``boxes=`` (in pixels of the ground
+    truth's grid) issues one more call right behind the metric launch, on the tensors that launch reads, and the result's
+    ``object_metrics`` ATTRIBUTE holds the ``ObjectMetrics`` (None otherwise); ``records`` and every field are what they were.  Pass it
+    by keyword."""
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None,
-                 point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
+                 object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -427,7 +456,8 @@ class PipelinedPredictor(_SlotPipeline):
     None unless ``want`` names "bin_edges" (the graph's static tensor is then copied per step).  Wants ``GPU_MAX_HW_QUEUES`` >= slots
     set before the HIP runtime starts, like ``PipelinedValidation``.  ``object_depth`` / ``submit(..., boxes=)``: as ``Predictor``'s; the
     readout runs on the slot's stream, a re-run step is read out from the re-run's map.  ``point_cloud`` / ``submit(..., intrinsics=)``:
-    likewise; a list of differently sized frames gives one launch pair per frame.
+    likewise; a list of differently sized frames gives one launch pair per frame.  ``object_metrics``: as ``Predictor``'s, on the slot's
+    stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.
 
         pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
         for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
@@ -440,12 +470,12 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
-                 crop: Optional[Tuple[int, int, int, int]] = None, point_cloud: Optional[dict] = None,
-                 object_depth: Optional[dict] = None):
+                 crop: Optional[Tuple[int, int, int, int]] = None, object_metrics: Optional[dict] = None,
+                 point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
@@ -475,8 +505,8 @@ class PipelinedPredictor(_SlotPipeline):
 
     def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None,
                intrinsics=None, boxes=None) -> None:
-        """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the readout boxes of the step's frames
-        (``object_depth`` keyword); lists are padded here, on the caller's stream, and the tensors are held like the frames.
+        """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the boxes of the step's frames
+        (``object_depth`` / ``object_metrics`` keywords); lists are padded here, on the caller's stream, and the tensors are held like the frames.
         ``intrinsics``: the frames' (fx, fy, cx, cy) for the point cloud (``point_cloud`` keyword), uploaded here and held likewise;
         the cloud's buffers are made per step on the slot's stream, its workspace is the slot's."""
         frames = _frame_list(frames_u8, "frames_u8", 4)
@@ -489,11 +519,10 @@ class PipelinedPredictor(_SlotPipeline):
         held += [] if K is None else [K]
         self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames)), first_image_id,
                      (object_features, object_xywh_list))
-        cloud = getattr(self._pending[-1].result, "points", None)
-        if cloud is not None:                                # made on the slot's stream, read by the caller on this one
-            for t in cloud:
-                if t is not None:
-                    t.record_stream(torch.cuda.current_stream(t.device))
+        made = self._pending[-1].result
+        for t in tuple(getattr(made, "points", None) or ()) + tuple((getattr(made, "object_metrics", None) or ())[:2]):
+            if t is not None:                                # made on the slot's stream, read by the caller on this one
+                t.record_stream(torch.cuda.current_stream(t.device))
 
     def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
         """The record table [N * B, 10] ([N * B, 16] with ``loss``) of collected results that carried ground truth."""
