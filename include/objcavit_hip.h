@@ -430,7 +430,12 @@ int ocv_depthwise_conv_nhwc_fwd(const float* in, const float* w, const float* bi
  *   gate[b][c] = sigmoid( b2[c] + sum_r w2t[r][c] * silu( b1[r] + sum_c' w1[r][c'] * mean[b][c'] ) ),
  *   mean[b][c] = (sum_tile part[b][tile][c]) / pixels_per_image.
  * w1 [R][C], w2t [R][C] (= conv_expand's weight transposed).  Replaces conv_dw + bn + act + se.conv_reduce / act /
- * conv_expand / sigmoid of the hub backbone's blocks (modules/DenseFeatureExtractor.py:18-27,149). */
+ * conv_expand / sigmoid of the hub backbone's blocks (modules/DenseFeatureExtractor.py:18-27,149).
+ * ocv_depthwise_set_dispatch(mode): which kernel these launches run -- 0 = automatic (k = 5: input rows staged once through
+ * LDS; k = 3: register window fed from global memory), 1 = register window everywhere, 2 = LDS rows wherever supported;
+ * anything else returns -1.  out / out_hl are bit-identical under every mode, the partial sums (and ocv_depthwise_sum_tiles)
+ * are not: the mode must not change between the size query and the launch.  Diagnostics / tests only. */
+int ocv_depthwise_set_dispatch(int mode);
 int ocv_depthwise_sum_tiles(int B, int C, int Ho, int Wo, int k, int stride);
 int ocv_depthwise_conv_nhwc_sum_fwd(const float* in, const float* w, const float* bias, float* out, float* part, int B,
                                     int C, int H, int W, int k, int stride, int pad_t, int pad_l, int Ho, int Wo,
