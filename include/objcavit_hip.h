@@ -221,7 +221,10 @@ int ocv_ffn_residual_layernorm_split3_fwd(const float* x, const void* w1_packed,
 /* Everything of a post-norm transformer layer that is local to a token, one launch per 32-token tile (split3 arithmetic):
  *   x1 = LayerNorm1(x + ctx Wo^T + bo);  out = LayerNorm2(x1 + W2 relu(W1 x1 + b1) + b2)   (rows with zero_row_mask != 0: 0)
  *   qkv_next[M][3E] = out . Wqkv_next^T + bqkv_next      when next_in_proj_p3 / next_in_proj_b / qkv_next are given
- * ctx = the attention output of the layer, x its input; p: the layer's parameters with the packed *_p3 weights set. */
+ * ctx = the attention output of the layer, x its input; p: the layer's parameters with the packed *_p3 weights set.
+ * zero_row_mask and a next projection exclude each other (all three ocv_layer_tail_* entry points return -1 before any launch):
+ * qkv_next is projected from the LayerNorm2 rows the kernel holds, NOT from the zeroed rows of `out`, and only the last layer of a
+ * masked stack zeroes rows -- the one layer without a next projection. */
 int ocv_layer_tail_split3_fwd(const float* ctx, const float* x, const ocv_encoder_layer_params* p, const void* next_in_proj_p3,
                               const float* next_in_proj_b, float eps, const uint8_t* zero_row_mask, float* out,
                               float* qkv_next, int M, int E, int FF, ocv_stream_t stream);

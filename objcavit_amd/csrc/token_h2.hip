@@ -343,7 +343,10 @@ extern "C" int ocv_layer_tail_h2_ws_fwd(const float* ctx, const float* x, const 
   OCV_CHECK_ARG(E == E128 && FF >= KC && FF % KC == 0, "ocv_layer_tail_h2_fwd: needs E = %d and FF a multiple of %d (got %d, %d)", E128, KC, E, FF);
   OCV_CHECK_ARG((next_in_proj_h2 == nullptr) == (qkv_next == nullptr) && (next_in_proj_h2 == nullptr || next_in_proj_b != nullptr),
                 "ocv_layer_tail_h2_fwd: next_in_proj_h2 / next_in_proj_b / qkv_next go together");
-  OCV_CHECK_ARG(M >= 0 && ocv_aligned16(ctx) && ocv_aligned16(x) && ocv_aligned16(out) && ocv_aligned16(qkv_next) &&
+  // (the kernel projects the LN2 tile it holds, not the zeroed rows it stores: only the last layer of a stack is masked, and it has no next)
+  OCV_CHECK_ARG(zero_row_mask == nullptr || qkv_next == nullptr,
+                "ocv_layer_tail_h2_fwd: zero_row_mask together with a next projection (qkv_next) is not supported");
+  OCV_CHECK_ARG(M >= 0&& ocv_aligned16(ctx) && ocv_aligned16(x) && ocv_aligned16(out) && ocv_aligned16(qkv_next) &&
                     ocv_aligned16(p->out_proj_h2) && ocv_aligned16(p->linear1_h2) && ocv_aligned16(p->linear2_h2) && ocv_aligned16(next_in_proj_h2),
                 "ocv_layer_tail_h2_fwd: bad M / alignment");
   if (M == 0) return 0;
