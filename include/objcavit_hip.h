@@ -566,6 +566,21 @@ int ocv_conv_nhwc_split_x_fwd(const void* x_hl, int Cin, const void* w_hi, const
  * tap t = 3 ky + kx, zeros beyond the ninth tap.  Same products, same fp32 accumulation; the K order differs from the tap-major form,
  * so results agree to rounding, not bit for bit. */
 int ocv_conv3x3_packed_taps_k(int Cin);
+/* HALO-STAGED dense 3 x 3 (conv_halo_dma_kernel): ocv_conv_nhwc_split_x_fwd with ksize 3 can run a second kernel whose workgroup is an
+ * image-aligned 8 x 32 pixel patch and stages the (8 + 2) x (32 + 2) halo patch of every 32-channel chunk ONCE, where the tap ring stages
+ * the 256 tile pixels nine times; the results are bit-identical.
+ * ocv_conv3x3_halo_supported: 1 where that kernel can run the shape (pure host arithmetic: H % 8 == 0, W % 32 == 0, a K axis below the
+ * length from which ocv_conv_nhwc_split_x_fwd considers split-K -- 9 ceil(Cin / 32) < 128 steps -- and that entry point's operand limits),
+ * else 0.  ocv_conv3x3_halo_lds_bytes: the dynamic LDS its launch requests.
+ * ocv_conv3x3_set_dispatch(mode): 0 = automatic (the halo kernel on the layers where it measured faster, keyed on H, W, Cin, Cout:
+ * 240 x 320 128 -> 128 and 120 x 160 256 -> 256; the tap ring everywhere else), 1 = the tap ring everywhere, 2 = the halo kernel -- an
+ * unsupported shape then FAILS (-1, ocv_last_error), it does not fall back; anything else returns -1.
+ * ocv_conv3x3_last_kernel: which kernel the last dense 3 x 3 launch of this process ran (1 = tap ring, 2 = halo-staged; 0 = none yet).
+ * The last three: diagnostics / tests only. */
+int ocv_conv3x3_halo_supported(int B, int H, int W, int Cin, int Cout);
+size_t ocv_conv3x3_halo_lds_bytes(void);
+int ocv_conv3x3_set_dispatch(int mode);
+int ocv_conv3x3_last_kernel(void);
 int ocv_conv3x3_split_packed_taps_fwd(const void* x_hl, int Cin, const void* w_hi, const void* w_lo, const float* oscale, int f16,
                                       const float* bias, const float* residual, float* y, void* y_hl, int B, int H, int W, int Cout,
                                       int act, ocv_stream_t stream);

@@ -46,6 +46,8 @@
 // tap -> (ky, kx) split and the source select are resolved at compile time.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 #include "../../include/objcavit_hip.h"
 
@@ -96,6 +98,7 @@ struct ConvArgs {
                                         // granules = 12 steps instead of 18 (their Cp = 32 / 64 multiply 25 % / 37 % zeros).  The weights
                                         // are ONE [Cout][Kp] matrix in the same granule order, Kp = steps x 32; gpt_inv = a 16.16
                                         // reciprocal of gpt, exact for every granule index of the launch (checked on the host).
+  int halo;                             // launch_conv: != 0 = conv_halo_dma_kernel (3 x 3, H % 8 == 0, W % 32 == 0; mtiles counts its patches)
 };
 
 // 16-byte global load (compiler-visible: hipcc tracks it and inserts the s_waitcnt before the first use).
@@ -424,8 +427,9 @@ __device__ __forceinline__ float conv_act(float v, int act) {
   if (act == OCV_ACT_RELU) return fmaxf(v, 0.f);
   return v;
 }
-template <bool F16>
-__device__ __forceinline__ void conv_store_rows(const ConvArgs& p, const unsigned char* lds, int wave, int lane, long m0, int n0,
+// ``rowm(R)``: the output pixel (row of the M x Cout result) of tile row R in [0, 256), >= p.M where the tile has none.
+template <bool F16, class RowMap>
+__device__ __forceinline__ void conv_store_rows(const ConvArgs& p, const unsigned char* lds, int wave, int lane, RowMap rowm, int n0,
                                                 long yoff) {
   const int cw = wave & 3, half = wave >> 2;
   const int wm = cw >> 1, wn = cw & 1;
@@ -443,7 +447,7 @@ __device__ __forceinline__ void conv_store_rows(const ConvArgs& p, const unsigne
 #pragma unroll 4
   for (int it = 0; it < 8; ++it) {
     const int row = half * 64 + it * 8 + rsub;
-    const long m = m0 + wm * 128 + row;
+    const long m = rowm(wm * 128 + row);
     if (m >= p.M) continue;
     f32x4 a = *reinterpret_cast<const f32x4*>(tile + row * ERS + oct * 8);
     f32x4 c = *reinterpret_cast<const f32x4*>(tile + row * ERS + oct * 8 + 4);
@@ -579,7 +583,7 @@ __global__ __launch_bounds__(512) void conv_split_dma_kernel(ConvArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) tile[(16 * i + 4 * q4 + r) * ERS + 16 * j + l15] = acc[i][j][r];
       __syncthreads();
-      conv_store_rows<F16>(p, lds, wave, lane, m0, n0, yoff);
+      conv_store_rows<F16>(p, lds, wave, lane, [m0](int R) { return m0 + R; }, n0, yoff);
       return;
     }
     // Cout not a multiple of 8: element-wise stores
@@ -758,7 +762,268 @@ __global__ __launch_bounds__(512) void conv_split_dma_kernel(ConvArgs p) {
 #undef OCV_WAIT_VM
   if ((p.Cout & 7) == 0) {                             // the consumers park their accumulators in LDS; all eight waves store
     __syncthreads();
-    conv_store_rows<F16>(p, lds, wave, lane, m0, n0, yoff);
+    conv_store_rows<F16>(p, lds, wave, lane, [m0](int R) { return m0 + R; }, n0, yoff);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// HALO-STAGED form of the dense 3 x 3 "same" convolution on a pre-split input (ks = 3, stride 1, ksplit = zbatch = 1, no
+// packed taps; H % 8 == 0, W % 32 == 0).  conv_split_dma_kernel tiles M as 256 flat-consecutive pixels and stages a complete
+// 256-row image of A for each of the nine taps of a 32-channel chunk: nine copies of the same pixels shifted by a row or
+// a column, 288 one-KiB pieces where the distinct pixels fill 44.  Here a workgroup is one image-aligned 8 x 32 pixel
+// patch x 128 output channels, and per chunk the producers stage the (8 + 2) x (32 + 2) HALO patch ONCE:
+//   LDS  A[2] (one per chunk parity): hi plane, lo plane, each 10 halo rows x 40 pixels (34 used) x 64 B = 25 600 B
+//        W[3] the weights' ring of one tap step each, as in conv_split_dma_kernel (hi 8 KiB, lo 8 KiB)
+//        2 x 51 200 + 3 x 16 384 = 151 552 B (the parked-accumulator epilogue uses the first 139 264 B, as there)
+//   tap (ky, kx): the fragment of tile pixel (ty, tx) is the LDS row (ty + ky) x 40 + tx + kx of the chunk's patch.
+//   Swizzle: stored 16-byte chunk = logical chunk ^ ((row >> 1) & 3), row = the LDS row.  A fragment read covers 16
+//   consecutive rows from ANY start (40 and 16 are multiples of 8: row & 7 = (tx + kx) & 7 whatever ty, ky and the
+//   fragment), and (row & 1) x 4 + (chunk ^ ((row >> 1) & 3)) runs over all eight 16-byte bank groups on any eight
+//   consecutive rows: conflict-free for all nine taps, and the key of a lane depends on kx alone (three pointers).
+// Pixels outside the image, and the six pad pixels of a halo row, come from ocv_zero_page: one mask bit per halo pixel
+// a lane fetches (it fetches the same 13 of them for every chunk).  Same eight specialised wavefronts, same MFMA sequence
+// per step (chunk outer, tap inner, hi hi / hi lo / lo hi) into the same accumulators: BIT-IDENTICAL results.  Patches run
+// in row-major order and the N-tiles of a patch share an XCD, so that neighbouring halos meet in L2.
+// ---------------------------------------------------------------------------
+constexpr int HTY = 8, HTX = 32, HPITCH = 40;                       // patch, LDS pixels per halo row
+constexpr int HROWS = (HTY + 2) * HPITCH;                           // 400 LDS rows per plane
+constexpr int HPLANE = HROWS * DROW, HABUF = 2 * HPLANE;            // 25600, 51200
+constexpr int HPIECES = 2 * HROWS / 16;                             // 50 one-KiB pieces per chunk (16 LDS rows of the hi or of the lo plane)
+constexpr int HAPW = (HPIECES + 3) / 4;                             // 13 per producer wavefront (the last two of 52 repeat piece 49)
+constexpr int HW0 = 2 * HABUF, HWSLOT = 2 * DB;                     // weights' ring: offset 102400, 16384 per slot
+constexpr int HLDS = HW0 + DNBUF * HWSLOT;                          // 151552
+static_assert(HROWS % 16 == 0 && HLDS <= 160 * 1024 && 4 * 128 * ERS * 4 <= HLDS, "conv_halo_dma_kernel: LDS budget");
+// A pieces of the NEXT chunk a producer wavefront issues beside tap step T's weight pieces: 2 2 2 2 2 1 1 1 0 = 13
+__host__ __device__ constexpr int halo_na(int T) { return T < 5 ? 2 : (T < 8 ? 1 : 0); }
+__host__ __device__ constexpr int halo_a0(int T) { return T < 5 ? 2 * T : 5 + T; }        // the first of them
+static_assert(halo_a0(8) == HAPW && halo_a0(7) + halo_na(7) == HAPW, "conv_halo_dma_kernel: A pieces per chunk");
+
+template <int N>
+__device__ __forceinline__ void halo_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+template <bool F16>
+__global__ __launch_bounds__(512) void conv_halo_dma_kernel(ConvArgs p) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int wg = blockIdx.x;
+  {
+    const int nwg = p.mtiles * p.ntiles;
+    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const int nchunk = p.Cp / CBK, nsteps = 9 * nchunk;
+  const int mt = wg / p.ntiles, nt = wg - mt * p.ntiles;
+  const int n0 = nt * CBN;
+  const int ppr = p.W / HTX, ppi = (p.H / HTY) * ppr;               // patches per patch row, per image
+  const int img = mt / ppi, prem = mt - img * ppi;
+  const int ty0 = (prem / ppr) * HTY, tx0 = (prem % ppr) * HTX;     // the patch's first pixel in its image
+  const long mbase = ((long)img * p.H + ty0) * p.W + tx0;
+  const int Wd = p.W;
+  auto rowm = [mbase, Wd](int R) { return mbase + (long)(R >> 5) * Wd + (R & 31); };      // tile row R = 32 ty + tx
+
+  if (wave < 4) {
+    // =========================== CONSUMERS: the MFMA sequence of conv_split_dma_kernel ===========================
+    // Fragment i of consumer (wm, wn) = tile rows 128 wm + 16 i + l15 = patch pixel (4 wm + (i >> 1), 16 (i & 1) + l15).
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l15 = lane & 15, q4 = lane >> 4;
+    unsigned aofs[3];                                               // per kx: this lane's byte offset in a plane, fragment 0, ky = 0
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+      aofs[kx] = (unsigned)(((wm * 4) * HPITCH + l15 + kx) * DROW + ((q4 ^ (((l15 + kx) >> 1) & 3)) * 16));
+    const unsigned char* pbw = lds + HW0 + (wn * 64 + l15) * DROW + ((q4 ^ ((l15 >> 1) & 3)) * 16);
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    __syncthreads();
+    for (int c = 0; c < nchunk; ++c) {
+      const unsigned char* abuf = lds + (c & 1) * HABUF;
+#pragma unroll 1
+      for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {                            // step 9 c + 3 ky + kx reads weight slot (step % 3) = kx
+          const unsigned char* pa = abuf + ky * (HPITCH * DROW) + aofs[kx];
+          const unsigned char* pb = pbw + kx * HWSLOT;
+          bf16x8 ah[8], al[8], bh[4], bl[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            bh[j] = *reinterpret_cast<const bf16x8*>(pb + j * 16 * DROW);
+            bl[j] = *reinterpret_cast<const bf16x8*>(pb + DB + j * 16 * DROW);
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            ah[i] = *reinterpret_cast<const bf16x8*>(pa + ((i >> 1) * HPITCH + (i & 1) * 16) * DROW);
+            al[i] = *reinterpret_cast<const bf16x8*>(pa + HPLANE + ((i >> 1) * HPITCH + (i & 1) * 16) * DROW);
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if constexpr (F16) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cv_h16x8, ah[i]), __builtin_bit_cast(cv_h16x8, bh[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cv_h16x8, ah[i]), __builtin_bit_cast(cv_h16x8, bl[j]), acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cv_h16x8, al[i]), __builtin_bit_cast(cv_h16x8, bh[j]), acc[i][j], 0, 0, 0);
+              } else {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+              }
+            }
+          __syncthreads();
+        }
+      }
+    }
+
+    // ---- epilogue: as conv_split_dma_kernel, with the patch's tile-row -> pixel map
+    if ((p.Cout & 7) == 0) {
+      float* tile = reinterpret_cast<float*>(lds) + wave * (128 * ERS);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) tile[(16 * i + 4 * q4 + r) * ERS + 16 * j + l15] = acc[i][j][r];
+      __syncthreads();
+      conv_store_rows<F16>(p, lds, wave, lane, rowm, n0, 0L);
+      return;
+    }
+    // Cout not a multiple of 8: element-wise stores (as conv_split_dma_kernel)
+    const long mlane = mbase + (long)(wm * 4) * Wd + 4 * q4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = n0 + wn * 64 + j * 16 + l15;
+      const bool nok = n < p.Cout;
+      const float bv = (p.bias != nullptr && nok) ? p.bias[n] : 0.f;
+      const float sv = (p.oscale != nullptr && nok) ? p.oscale[n] : 1.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long m = mlane + (i >> 1) * Wd + ((i & 1) * 16 + r);       // = rowm(128 wm + 16 i + 4 q4 + r)
+          if (nok) {
+            float v = fmaf(acc[i][j][r], sv, bv);
+            if (p.act == OCV_ACT_LEAKY_RELU) v = v > 0.f ? v : 0.01f * v;
+            else if (p.act == OCV_ACT_SILU) v = fast_silu(v);
+            else if (p.act == OCV_ACT_RELU) v = fmaxf(v, 0.f);
+            if (p.res != nullptr) v += p.res[m * p.Cout + n];
+            if (p.y != nullptr) p.y[m * p.Cout + n] = v;
+            if (p.yhl != nullptr) {
+              if constexpr (F16) {
+                ocv_range_note(p.range_flag, fabsf(v));
+                _Float16* yh = reinterpret_cast<_Float16*>(p.yhl);
+                const _Float16 hb = (_Float16)v;
+                yh[hl_index(m, n, p.Cpo)] = hb;
+                yh[hl_index(m, n, p.Cpo) + 32] = (_Float16)(v - (float)hb);
+              } else {
+                const __bf16 hb = (__bf16)v;
+                p.yhl[hl_index(m, n, p.Cpo)] = hb;
+                p.yhl[hl_index(m, n, p.Cpo) + 32] = (__bf16)(v - (float)hb);
+              }
+            }
+          }
+        }
+    }
+    return;
+  }
+
+  // =========================== PRODUCERS (LDS-DMA issuers) ===========================
+  // A: piece q of a chunk = plane q & 1 (hi, lo), LDS rows [16 (q >> 1), +16) of it; wavefront pw owns pieces 4 j + pw,
+  // j < 13 (52 slots for 50 pieces: slots 50 and 51 fetch piece 49 a second time -- the same bytes to the same place).
+  // The hi and the lo half of a pixel's 128-byte line are fetched by two wavefronts in the same step, so that the second
+  // can hit in L1.  Lane L of a piece is LDS row 16 (q >> 1) + (L >> 2) = halo pixel (row / 40, row % 40), stored chunk L & 3 = logical chunk
+  // (L & 3) ^ ((L >> 3) & 3) (piece bases are multiples of 16 rows).  The lane's source offsets and in-image bits do not
+  // depend on the chunk: computed once.  B: rows [32 pw, +32) of the step's weights, 4 pieces, as conv_split_dma_kernel.
+  const int pw = wave - 4;
+  const int lrow = lane >> 2;
+  const int lchunk = (lane & 3) ^ ((lane >> 3) & 3);
+  unsigned aoff[HAPW], amask = 0, adst[HAPW];
+#pragma unroll
+  for (int j = 0; j < HAPW; ++j) {
+    const int q = min(4 * j + pw, HPIECES - 1);
+    const int plane = q & 1, pc = q >> 1;
+    const int hp = pc * 16 + lrow, hy = hp / HPITCH, hx = hp - hy * HPITCH;
+    const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
+    const bool ok = hx < HTX + 2 && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+    aoff[j] = (((unsigned)img * (unsigned)p.H + (unsigned)y) * (unsigned)p.W + (unsigned)x) * (unsigned)(4 * p.Cp) +
+              (unsigned)(plane * 64 + lchunk * 16);                 // (operands are below 4 GiB; unused where !ok)
+    amask |= ok ? 1u << j : 0u;
+    adst[j] = (unsigned)(plane * HPLANE + pc * 1024);               // wave-uniform
+  }
+  unsigned rbB[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int bn = min(n0 + 32 * pw + 16 * i + lrow, p.Cout - 1);
+    rbB[i] = (unsigned)(((long)bn * p.Cp + lchunk * 8) * 2);
+  }
+  const unsigned wtap = (unsigned)((long)p.Cout * p.Cp * 2);
+  const char* xz = (const char*)p.xhl;
+  const char* whz = (const char*)p.whi;
+  const char* wlz = (const char*)p.wlo;
+
+  auto issue_a = [&](int j, int c) {                                // piece j of this wavefront, chunk c (j: a constant after unrolling)
+    const void* src = ((amask >> j) & 1u) ? (const void*)(xz + aoff[j] + (unsigned)c * 128u) : (const void*)ocv_zero_page;
+    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds + (c & 1) * HABUF + adst[j]), 16, 0, 0);
+  };
+  auto issue_w = [&](int tap, int c) {                              // the weights of step 9 c + tap into slot tap % 3
+    const unsigned woff = (unsigned)tap * wtap + (unsigned)c * (CBK * 2);
+    unsigned char* base = lds + HW0 + (tap % 3) * HWSLOT;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      unsigned char* dst = base + (32 * pw + 16 * i) * DROW;
+      __builtin_amdgcn_global_load_lds((gptr_t)(whz + woff + rbB[i]), (lptr_t)dst, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(wlz + woff + rbB[i]), (lptr_t)(dst + DB), 16, 0, 0);
+    }
+  };
+
+  // Interval s = 9 c + T (consumers on weight slot T % 3 and A buffer c & 1).  The producers issue, in this order,
+  //   halo_na(T) A pieces of chunk c + 1 into A buffer (c + 1) & 1 -- last read in chunk c - 1, free since the barrier that
+  //                                                                  opened chunk c
+  //   the 4 weight pieces of step s + 2 into slot (s + 2) % 3       -- last read in interval s - 1
+  // and then wait for step s + 1's weights, issued a whole interval earlier: everything but this interval's own pieces,
+  //   T = 0..4  vmcnt(6)   T = 5..7  vmcnt(5)   T = 8  vmcnt(4)     (4 where there is no next chunk, 0 on the last two steps)
+  // followed by a raw s_barrier.  At T = 8 only the weights of s + 2 stay in flight: every A piece of chunk c + 1 (issued
+  // at T <= 7) has landed before the barrier behind which the consumers first read it.
+  auto step = [&](auto tc, int c) {
+    constexpr int T = decltype(tc)::value;
+    const bool nxt = c + 1 < nchunk;
+    if (nxt) {
+#pragma unroll
+      for (int k = 0; k < halo_na(T); ++k) issue_a(halo_a0(T) + k, c + 1);
+    }
+    if (9 * c + T + 2 < nsteps) {
+      issue_w((T + 2) % 9, c + (T + 2) / 9);
+      if (nxt) halo_wait_vm<4 + halo_na(T)>();
+      else halo_wait_vm<4>();
+    } else {
+      halo_wait_vm<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+  };
+
+  // prologue: all of chunk 0's A, the weights of steps 0 and 1; step 1's may stay in flight
+#pragma unroll
+  for (int j = 0; j < HAPW; ++j) issue_a(j, 0);
+  issue_w(0, 0);
+  issue_w(1, 0);
+  halo_wait_vm<4>();
+  __builtin_amdgcn_s_barrier();
+  for (int c = 0; c < nchunk; ++c) {
+    step(std::integral_constant<int, 0>{}, c);
+    step(std::integral_constant<int, 1>{}, c);
+    step(std::integral_constant<int, 2>{}, c);
+    step(std::integral_constant<int, 3>{}, c);
+    step(std::integral_constant<int, 4>{}, c);
+    step(std::integral_constant<int, 5>{}, c);
+    step(std::integral_constant<int, 6>{}, c);
+    step(std::integral_constant<int, 7>{}, c);
+    step(std::integral_constant<int, 8>{}, c);
+  }
+  if ((p.Cout & 7) == 0) {                             // the consumers park their accumulators in LDS; all eight waves store
+    __syncthreads();
+    conv_store_rows<F16>(p, lds, wave, lane, rowm, n0, 0L);
   }
 }
 
@@ -817,14 +1082,32 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(FinArgs p) {
 namespace {
 // Split-K pays when the tile count leaves the last round of workgroups mostly empty: 600 tiles on 256 CUs run three
 // rounds for 2.34 rounds of work; as 1200 half-K workgroups they run five half-rounds = 2.5.  Returns 1 or 2.
+constexpr int KSPLIT_MIN_STEPS = 128;           // split-K is considered from this many K steps on
 int conv_ksplit(long M, int Cout, int Cin, int ksize) {
   const long tiles = (long)ocv_cdiv(M, CBM) * ocv_cdiv(Cout, CBN);
   const int nsteps = ksize * ksize * ((Cin + CBK - 1) / CBK);
-  if ((Cout & 7) != 0 || nsteps < 128 || tiles <= 256) return 1;
+  if ((Cout & 7) != 0 || nsteps < KSPLIT_MIN_STEPS || tiles <= 256) return 1;
   const double c1 = (double)((tiles + 255) / 256), c2 = (double)((2 * tiles + 255) / 256) / 2.0;
   return c2 <= 0.9 * c1 ? 2 : 1;
 }
-// conv_split_dma_kernel (pre-split input)
+// 0 = automatic, 1 = conv_split_dma_kernel (the tap ring) everywhere, 2 = conv_halo_dma_kernel, an error where it cannot run
+// (ocv_conv3x3_set_dispatch)
+int g_conv3x3_dispatch = 0;
+
+// The dense 3 x 3 layers that automatic dispatch gives to conv_halo_dma_kernel: those measured faster than the tap ring
+// by the project's rule (every run faster, by more than twice the run-to-run spread; profiles/conv_halo.txt), keyed on
+// (H, W, Cin, Cout).  The batch is not part of the key: both kernels run B H W / 256 workgroups of the same K length, so
+// the grid scales with B under either and the per-workgroup difference is what was measured (at B = 16 by the rule; at
+// B = 4 and 8 every run was faster too, three of those four cells by the rule: same file).
+bool conv_halo_auto(int /*B*/, int H, int W, int Cin, int Cout) {
+  static const int won[][4] = {{240, 320, 128, 128}, {120, 160, 256, 256}};
+  for (const auto& s : won)
+    if (H == s[0] && W == s[1] && Cin == s[2] && Cout == s[3]) return true;
+  return false;
+}
+int g_conv3x3_last_kernel = 0;                  // ocv_conv3x3_last_kernel
+
+// conv_split_dma_kernel (pre-split input), or conv_halo_dma_kernel where the entry point chose it (ConvArgs::halo)
 int launch_conv(ConvArgs& a, int B, hipStream_t st) {
   a.Cp = (a.Cin + CBK - 1) / CBK * CBK;
   a.M = (long)B * a.H * a.W;
@@ -833,7 +1116,18 @@ int launch_conv(ConvArgs& a, int B, hipStream_t st) {
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)conv_split_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv_split_dma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv_halo_dma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv_halo_dma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
+  }
+  if (a.ks == 3 && a.gpt == 0) g_conv3x3_last_kernel = a.halo ? 2 : 1;
+  if (a.halo) {                                   // M = 256 x patches exactly (H % 8 == 0, W % 32 == 0): mtiles is the patch count
+    if (a.f16)
+      hipLaunchKernelGGL(conv_halo_dma_kernel<true>, dim3(a.mtiles * a.ntiles), dim3(512), HLDS, st, a);
+    else
+      hipLaunchKernelGGL(conv_halo_dma_kernel<false>, dim3(a.mtiles * a.ntiles), dim3(512), HLDS, st, a);
+    OCV_CHECK_LAUNCH("ocv_conv_nhwc");
+    return 0;
   }
   if (a.ksplit < 1) a.ksplit = 1;
   if (a.zbatch < 1) a.zbatch = 1;
@@ -875,6 +1169,28 @@ extern "C" size_t ocv_conv_nhwc_split_workspace_bytes(int B, int H, int W, int C
   return ks > 1 ? (size_t)ks * M * Cout * sizeof(float) : 0;
 }
 
+// conv_halo_dma_kernel: whether it can run a dense 3 x 3 "same" convolution of this shape (pure host arithmetic) -- whole
+// 8 x 32 patches, the operand limits of ocv_conv_nhwc_split_x_fwd, and a K axis below the length from which that entry
+// point considers split-K (9 x ceil(Cin / 32) < KSPLIT_MIN_STEPS, the threshold of conv_ksplit).
+extern "C" int ocv_conv3x3_halo_supported(int B, int H, int W, int Cin, int Cout) {
+  if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return 0;
+  if (H % HTY != 0 || W % HTX != 0 || 9 * ((Cin + CBK - 1) / CBK) >= KSPLIT_MIN_STEPS) return 0;
+  if ((long)B * H * W * (Cin + 32) * 4 >= (1L << 32) || 9L * Cout * (Cin + 32) * 2 >= (1L << 32)) return 0;
+  return 1;
+}
+
+extern "C" size_t ocv_conv3x3_halo_lds_bytes(void) { return (size_t)HLDS; }
+
+// 1 = conv_split_dma_kernel, 2 = conv_halo_dma_kernel: the kernel the last dense (not packed-tap) 3 x 3 launch of this
+// process ran; 0 before the first.  Tests / tools only.
+extern "C" int ocv_conv3x3_last_kernel(void) { return g_conv3x3_last_kernel; }
+
+extern "C" int ocv_conv3x3_set_dispatch(int mode) {
+  OCV_CHECK_ARG(mode >= 0 && mode <= 2, "ocv_conv3x3_set_dispatch: mode must be 0 (automatic), 1 (tap ring) or 2 (halo-staged), got %d", mode);
+  g_conv3x3_dispatch = mode;
+  return 0;
+}
+
 extern "C" int ocv_conv_nhwc_split_x_fwd(const void* x_hl, int Cin, const void* w_hi, const void* w_lo, const float* oscale,
                                          int f16, const float* bias, const float* residual, float* y, void* y_hl, int B, int H,
                                          int W, int Cout, int ksize, int act, void* workspace, size_t workspace_bytes,
@@ -887,6 +1203,12 @@ extern "C" int ocv_conv_nhwc_split_x_fwd(const void* x_hl, int Cin, const void* 
   OCV_CHECK_ARG((reinterpret_cast<uintptr_t>(x_hl) & 127) == 0 && ocv_aligned16(w_hi) && ocv_aligned16(w_lo), "ocv_conv_nhwc_split_fwd: x_hl must be 128-byte aligned, weights 16-byte aligned");
   OCV_CHECK_ARG((long)B * H * W * (Cin + 32) * 4 < (1L << 32) && 9L * Cout * (Cin + 32) * 2 < (1L << 32), "ocv_conv_nhwc_split_fwd: each operand must be smaller than 4 GiB");
   OCV_CHECK_ARG(f16 == 0 || f16 == 1, "ocv_conv_nhwc_split_fwd: f16 must be 0 (bf16 pairs) or 1 (fp16 pairs)");
+  bool use_halo = false;                          // dense 3 x 3: conv_halo_dma_kernel where forced, or where automatic picks it
+  if (ksize == 3 && g_conv3x3_dispatch != 1) {
+    const bool can = ocv_conv3x3_halo_supported(B, H, W, Cin, Cout) != 0;
+    OCV_CHECK_ARG(can || g_conv3x3_dispatch != 2, "ocv_conv_nhwc_split_fwd: the halo-staged 3x3 kernel is forced (ocv_conv3x3_set_dispatch(2)) and cannot run B %d, %d x %d, %d -> %d channels (ocv_conv3x3_halo_supported: H %% 8 == 0, W %% 32 == 0, fewer than %d K steps)", B, H, W, Cin, Cout, KSPLIT_MIN_STEPS);
+    use_halo = can && (g_conv3x3_dispatch == 2 || conv_halo_auto(B, H, W, Cin, Cout));
+  }
   ConvArgs a{};
   a.xhl = (const __bf16*)x_hl; a.yhl = (__bf16*)y_hl; a.Cpo = (Cout + 31) / 32 * 32;
   a.whi = (const __bf16*)w_hi; a.wlo = (const __bf16*)w_lo; a.bias = bias; a.res = residual; a.y = y;
@@ -896,6 +1218,10 @@ extern "C" int ocv_conv_nhwc_split_x_fwd(const void* x_hl, int Cin, const void* 
   if (y_hl != nullptr && Cout % 32 != 0) {       // the kernels write channels < Cout only: pad channels must read as zero
     const int zrc = ocv_zero_async(y_hl, ocv_split_act_elems(B, H, W, Cout) * sizeof(__bf16), (hipStream_t)stream);          // (a launch, not a memset node: common.hpp)
     if (zrc != 0) return zrc;
+  }
+  if (use_halo) {
+    a.halo = 1;                                   // (supported: below the K length from which split-K is considered)
+    return launch_conv(a, B, (hipStream_t)stream);
   }
   const long M = (long)B * H * W;
   const int ks = conv_ksplit(M, Cout, Cin, ksize);
