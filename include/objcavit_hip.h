@@ -829,6 +829,42 @@ int ocv_object_tokens_pad_fwd(const float* tokens, const int* counts, float pad_
                               int capacity, int E, ocv_stream_t stream);
 int ocv_object_front_pad_fwd(const float* objects, const int* counts, int group, int nmax, float pad_value, float* out,
                              uint8_t* key_padding_mask, int B, int capacity, int S, int E, ocv_stream_t stream);
+/* Object front end: a detector's SELECTED detections -> the padded object inputs above, in one launch (what the reference does per
+ * object on the host: the size relation of modules/ObjectLanguageStrategy.py:69-81, the phrase -> text feature step as a table lookup,
+ * the <UNK> object of an image without detections, modules/LanguageEmbeddingWrapper.py:56-61 + modules/ObjCAViT.py:311-315).
+ * Inputs, all in DEVICE memory and read by the kernel only: box r of image b = xywh[(b * cap + r) * xywh_row_stride + 0..3] (centre x,
+ * centre y, width, height), cls int32 [B][cap], counts int32 [B] (read as clamp(count, 0, cap); rows at or beyond it are never read).
+ * Tables, element type fp32 (f16 = 0) or fp16 (f16 = 1, widened exactly), rows of F elements, 16-byte aligned:
+ *   dense mode (no hash table): class_table [n_classes][F], row = cls.
+ *   hash mode (hash_keys / hash_rows / hash_features all given): key = cls << 24 | next << 3 | (rel + 1), looked up by linear probing
+ *     from  splitmix64_finaliser(key) & (slots - 1)  in hash_keys uint64 [slots] (slots a power of two, an empty slot = all ones);
+ *     hash_rows int32 [slots] names a row of hash_features [n_rows][F].  class_table, when given, is the FALLBACK of a miss.
+ *   rel / next: with a hash table and >= 2 live rows, ratio = fp32(fp32(w * h) / fp32(w' * h')) against the NEXT live row (cyclic), both
+ *     operations IEEE-rounded; rel = the number of thresholds[k] <= ratio (thresholds: HOST array of six increasing fp32 values, copied
+ *     by value; the steps of the reference's log / round / clip formula), next = that row's class.  Otherwise, and for a ratio that is
+ *     not a finite positive number (flag BAD_RATIO; the reference raises), rel = -1 and next = cls.
+ * Outputs: B' = B images, or 2 B when mirror_width > 0: image b + B = image b with centre x -> fp32(mirror_width - cx), same order.
+ *   features[bo * feat_image_stride + j * feat_row_stride + 0..F), xywh_out[bo * xywh_out_image_stride + j * xywh_out_row_stride + 0..3],
+ *   j < cap: the table row (else the fallback row, else zeros) and the box unchanged for a live row; zeros for a row at or beyond the
+ *   count -- except row 0 of an image whose count is 0: zero feature, box (-1, -1, -1, -1).  Rows cap .. cap_out - 1 and columns
+ *   beyond the fourth are NOT touched (cap_out >= cap: the launch may write straight into larger buffers).
+ *   counts_out int32 [B'] = clamp(count, 1, cap).  rows int32 [B'][cap] = the table row, -1 on a miss and beyond the count; keys uint64
+ *   [B'][cap] = the key (all ones beyond the count or when a class is invalid); flags uint8 [B'][cap], an OR of OCV_OBJFE_*:
+ *   MISS (no table row), BAD_CLASS (cls, or the next row's, outside [0, n_classes): no key, a miss; the fallback row of cls if cls itself
+ *   is valid), BAD_RATIO, COUNT_CLAMPED (row 0 only: count > cap).
+ * One launch of B' * cap workgroups, no workspace, no allocation, no synchronisation, no atomics, one writer per element: bit-equal
+ * on repeat.  -1 with a message before any launch on: a null pointer, no table or half a hash table, F not a positive multiple of 4,
+ * n_classes outside [1, 2^20], slots not a power of two, cap_out < cap, bad strides, bad thresholds, a bad mirror_width, misalignment. */
+#define OCV_OBJFE_MISS 1
+#define OCV_OBJFE_BAD_CLASS 2
+#define OCV_OBJFE_BAD_RATIO 4
+#define OCV_OBJFE_COUNT_CLAMPED 8
+int ocv_object_frontend_fwd(const float* xywh, long xywh_row_stride, const int* cls, const int* counts, int B, int cap,
+                            const void* class_table, int n_classes, const uint64_t* hash_keys, const int* hash_rows, int slots,
+                            const void* hash_features, int n_rows, const float* thresholds, int f16, int F, float mirror_width,
+                            float* features, long feat_image_stride, long feat_row_stride, float* xywh_out, long xywh_out_image_stride,
+                            long xywh_out_row_stride, int* counts_out, int cap_out, int* rows, uint64_t* keys, uint8_t* flags,
+                            ocv_stream_t stream);
 
 /* Positional-embedding samplers of GridRandomPositionalEmbeddings.forward (modules/ObjCAViT.py:50-147) on the learnable
  * table `table` [>= gh*gw][E], viewed as a gh x gw grid of E-vectors (row y*gw + x; reference :82-83).  One output row

@@ -160,6 +160,9 @@ PROTOTYPES = {
     "ocv_bin_edges_fwd": (C.c_int, [_f32p, C.c_int, C.c_float, C.c_float, _f32p, _f32p, _f32p, C.c_int, C.c_int, _stream]),
     "ocv_object_tokens_pad_fwd": (C.c_int, [_f32p, C.c_void_p, C.c_float, _f32p, _u8p, C.c_int, C.c_int, C.c_int, _stream]),
     "ocv_object_front_pad_fwd": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_int, C.c_float, _f32p, _u8p] + [C.c_int] * 4 + [_stream]),
+    "ocv_object_frontend_fwd": (C.c_int, [_f32p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, _f32p, C.c_long,
+                                          C.c_long, _f32p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _u8p, _stream]),
     "ocv_split_act_elems": (C.c_size_t, [C.c_int] * 4),
     "ocv_conv_nhwc_split_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _f32p, _f32p, _f32p, C.c_void_p]
                                 + [C.c_int] * 6 + [_stream]),

@@ -10,7 +10,8 @@ the decoder still ran on MIOpen / ATen kernels replay was SLOWER than eager, 77 
 kernel eagerly after each replay.  Objects: by default whatever the model's provider returned at capture time is baked in as
 static device tensors (the benchmark's synthetic objects).  With ``object_capacity = N`` the graph owns static PADDED object
 buffers ([B, N, 512] features, [B, N, 4] boxes, int32 counts[B]) and every replay takes LIVE objects -- ``g(image, features_list,
-xywh_list)`` / ``g(image, PaddedObjects)`` / the provider's output for ``image`` -- copied into those buffers first: the masks and
+xywh_list)`` / ``g(image, PaddedObjects)`` / the provider's output for ``image`` -- copied into those buffers first (or, for
+``g(image, Detections)``, written there by the one launch of the model's ``DeviceObjectProvider``): the masks and
 the front-padding of the key rows are formed on the device from ``counts`` (csrc/objects_pad.hip), nothing on the captured path
 depends on a count on the host, so ONE capture per (B, N) serves any ragged object set (BASELINE configs[4]: a detector + CLIP
 in front of a hipGraph-captured forward, modules/GraphBins.py:90-107, modules/ObjCAViT.py:311-330,180-194).  Launches named in ``eager_ops`` (timing names of hip_ops, e.g.
@@ -31,6 +32,7 @@ import torch
 
 from . import graph_topology, hip_ops
 from .modules.ObjCAViT import PaddedObjects
+from .objects import Detections, DeviceObjectProvider
 
 # Stream capture is a process-wide affair on ROCm 7.2: two threads capturing at the same time abort inside capture_end
 # (measured: tests, round 3), whatever capture_error_mode says.  Captures are therefore serialised; everything a capture
@@ -206,11 +208,24 @@ class GraphedGraphBins:
         """Copy one batch's objects into the graph's static buffers (current stream): a ``PaddedObjects`` of at most the graph's
         capacity, the reference's two lists (``object_xywh_list`` None = no boxes: every image carries the <UNK> box), or None = ask
         the model's provider (for ``image``, default the static image).  Device counts are not read back here: the kernels take
-        them as min(max(count, 1), capacity) (csrc/objects_pad.hip), so a stray 0 cannot mask every key of an image."""
+        them as min(max(count, 1), capacity) (csrc/objects_pad.hip), so a stray 0 cannot mask every key of an image.
+        A ``Detections`` (objects.py) is handed to the model's ``DeviceObjectProvider``, which writes features, boxes and counts
+        straight into the static buffers: one launch, no intermediate tensor, no ``copy_``; rows beyond the detections' capacity
+        keep what they held (they lie beyond every count that launch writes)."""
         if self.objects is None:
             raise RuntimeError("this graph was captured with its objects baked in (no object_capacity): it takes only the image")
         st = self.objects
         B, cap = st.features.shape[:2]
+        if isinstance(object_features, Detections):
+            prov = self.model.object_provider
+            if not isinstance(prov, DeviceObjectProvider):
+                raise TypeError("Detections as object_features need the model's object_provider to be a DeviceObjectProvider "
+                                f"(it holds the tables), not {type(prov).__name__}")
+            if prov.images_out(object_features) != B or object_features.capacity > cap or prov.dim != st.features.shape[2]:
+                raise ValueError(f"captured for objects [{B}, <= {cap}, {st.features.shape[2]}], got detections for "
+                                 f"{prov.images_out(object_features)} image(s) of up to {object_features.capacity} x {prov.dim}")
+            prov.write(object_features, st)
+            return
         if object_features is None:
             img = self.static_image if image is None else image
             padded = getattr(self.model.object_provider, "padded", None)

@@ -380,6 +380,90 @@ def object_front_pad(objects: torch.Tensor, counts: torch.Tensor, S: int, pad_va
     return out, kpm
 
 
+def object_frontend(xywh: torch.Tensor, cls: torch.Tensor, counts: torch.Tensor, class_table: Optional[torch.Tensor] = None,
+                    phrases=None, fallback: Optional[torch.Tensor] = None, mirror_width: Optional[float] = None,
+                    out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """Selected detections -> padded object inputs in ONE launch (csrc/object_frontend.hip; include/objcavit_hip.h states every rule).
+    xywh fp32 [B, cap, >= 4] (rows may be strided), cls int32 [B, cap], counts int32 [B].  Exactly one of ``class_table`` [n_classes,
+    F] (row = class) and ``phrases`` (an ``objects.PhraseTable``: the (class, next class, size relation) hash table); with
+    ``phrases``, ``fallback`` [n_classes, F] serves a miss.  Tables are fp32 or fp16, one element type per call.  ``mirror_width``
+    W > 0: B' = 2 B images, image b + B = image b with cx -> W - cx; else B' = B.  ``out`` = (features [B', cap_out, F], xywh [B',
+    cap_out, >= 4], counts int32 [B']) with cap_out >= cap to write into (a captured graph's static buffers: rows beyond cap are
+    not touched), else they are allocated at cap_out = cap.
+    -> (features, xywh, counts, rows int32 [B', cap] (-1 = miss), keys uint64 [B', cap], flags uint8 [B', cap])."""
+    lib = _lib.load()
+    _req(xywh, "xywh", contiguous=False); _req(cls, "cls", torch.int32); _req(counts, "counts", torch.int32)
+    if xywh.dim() != 3 or xywh.shape[2] < 4 or tuple(cls.shape) != tuple(xywh.shape[:2]) or tuple(counts.shape) != (xywh.shape[0],):
+        raise ValueError("object_frontend: expected xywh [B, cap, >= 4], cls [B, cap], counts [B]")
+    B, cap = int(xywh.shape[0]), int(xywh.shape[1])
+    if B < 1 or cap < 1:
+        raise ValueError("object_frontend: B and cap must be >= 1")
+    if xywh.stride(2) != 1 or xywh.stride(1) < 4 or (B > 1 and xywh.stride(0) != cap * xywh.stride(1)):
+        xywh = xywh[:, :, :4].contiguous()
+    if (class_table is None) == (phrases is None):
+        raise ValueError("object_frontend: give exactly one of class_table / phrases")
+    if fallback is not None and phrases is None:
+        raise ValueError("object_frontend: fallback goes with phrases")
+    dense = class_table if phrases is None else fallback
+    main = class_table if phrases is None else phrases.features
+    if phrases is not None and (phrases.keys is None or phrases.features is None):
+        raise ValueError("object_frontend: the PhraseTable was built without a device")
+    if main.dtype not in (torch.float32, torch.float16):
+        raise TypeError("object_frontend: tables are float32 or float16")
+    _req(main, "table", main.dtype)
+    if main.dim() != 2 or main.shape[1] < 4 or main.shape[1] % 4:
+        raise ValueError("object_frontend: a table must be [rows, F] with F a positive multiple of 4")
+    F = int(main.shape[1])
+    n_classes = int(class_table.shape[0]) if phrases is None else int(phrases.n_classes)
+    if dense is not None:
+        _req(dense, "class_table" if phrases is None else "fallback", main.dtype)
+        if tuple(dense.shape) != (n_classes, F):
+            raise ValueError(f"object_frontend: class_table / fallback must be [{n_classes}, {F}] in the table's element type")
+    if not 1 <= n_classes <= (1 << 20):
+        raise ValueError("object_frontend: n_classes outside [1, 2^20]")
+    slots = n_rows = 0
+    thr = None
+    if phrases is not None:
+        _req(phrases.keys, "phrases.keys", torch.int64); _req(phrases.rows, "phrases.rows", torch.int32)
+        slots, n_rows = int(phrases.keys.shape[0]), int(main.shape[0])
+        if slots < 2 or slots & (slots - 1) or tuple(phrases.rows.shape) != (slots,):
+            raise ValueError("object_frontend: the hash table's slots must be a power of two, keys and rows of that length")
+        from ..objects import REL_SIZE_THRESHOLDS
+        thr = (C.c_float * 6)(*REL_SIZE_THRESHOLDS)
+    W = 0.0 if mirror_width is None else float(mirror_width)
+    if not (W >= 0.0 and W < float("inf")) or (mirror_width is not None and W == 0.0):
+        raise ValueError("object_frontend: mirror_width must be a positive, finite width")
+    Bo = 2 * B if W > 0.0 else B
+    dev = xywh.device
+    if out is None:
+        feats = torch.empty(Bo, cap, F, dtype=torch.float32, device=dev)
+        boxes = torch.empty(Bo, cap, 4, dtype=torch.float32, device=dev)
+        cnt = torch.empty(Bo, dtype=torch.int32, device=dev)
+    else:
+        feats, boxes, cnt = out
+        _req(feats, "out features", contiguous=False); _req(boxes, "out xywh", contiguous=False); _req(cnt, "out counts", torch.int32)
+        if (feats.dim() != 3 or boxes.dim() != 3 or feats.shape[0] != Bo or feats.shape[1] < cap or feats.shape[2] != F
+                or tuple(boxes.shape[:2]) != tuple(feats.shape[:2]) or boxes.shape[2] < 4 or tuple(cnt.shape) != (Bo,)):
+            raise ValueError(f"object_frontend: out must be features [{Bo}, >= {cap}, {F}], xywh [{Bo}, the same, >= 4], counts [{Bo}]; got "
+                             f"{tuple(feats.shape)}, {tuple(boxes.shape)}, {tuple(cnt.shape)}")
+        for t, name in ((feats, "features"), (boxes, "xywh")):      # rows may be strided (a column slice, a larger buffer), never overlapping
+            if t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < t.shape[1] * t.stride(1):
+                raise ValueError(f"object_frontend: out {name} must have unit-stride rows that do not overlap, got strides {t.stride()}")
+    cap_out = int(feats.shape[1])
+    rows = torch.empty(Bo, cap, dtype=torch.int32, device=dev)
+    keys = torch.empty(Bo, cap, dtype=torch.int64, device=dev)
+    flags = torch.empty(Bo, cap, dtype=torch.uint8, device=dev)
+    with timed("object_frontend"):
+        check(lib.ocv_object_frontend_fwd(xywh.data_ptr(), xywh.stride(1), cls.data_ptr(), counts.data_ptr(), B, cap, _ptr(dense), n_classes,
+                                          None if phrases is None else phrases.keys.data_ptr(),
+                                          None if phrases is None else phrases.rows.data_ptr(), slots,
+                                          None if phrases is None else main.data_ptr(), n_rows, thr, int(main.dtype == torch.float16), F,
+                                          W, feats.data_ptr(), feats.stride(0), feats.stride(1), boxes.data_ptr(), boxes.stride(0),
+                                          boxes.stride(1), cnt.data_ptr(), cap_out, rows.data_ptr(), keys.data_ptr(), flags.data_ptr(),
+                                          _stream()), "ocv_object_frontend_fwd")
+    return feats, boxes, cnt, rows, keys.view(torch.uint64), flags
+
+
 # ---------------------------------------------------------------------------
 # positional-embedding samplers (GridRandomPositionalEmbeddings)
 # ---------------------------------------------------------------------------

@@ -508,7 +508,9 @@ class PipelinedPredictor(_SlotPipeline):
         """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the boxes of the step's frames
         (``object_depth`` / ``object_metrics`` keywords); lists are padded here, on the caller's stream, and the tensors are held like the frames.
         ``intrinsics``: the frames' (fx, fy, cx, cy) for the point cloud (``point_cloud`` keyword), uploaded here and held likewise;
-        the cloud's buffers are made per step on the slot's stream, its workspace is the slot's."""
+        the cloud's buffers are made per step on the slot's stream, its workspace is the slot's.
+        ``object_features``: as ``PipelinedValidation.submit``'s -- a ``Detections`` of the B frames (the model's provider a
+        ``DeviceObjectProvider``, with ``mirror_width`` under flip-TTA) is written into the slot's static buffers by one launch."""
         frames = _frame_list(frames_u8, "frames_u8", 4)
         if sum(int(f.shape[0]) for f in frames) != self.B or self.ends.window_of(frames) != self.size:
             raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")

@@ -280,7 +280,9 @@ class PipelinedValidation(_SlotPipeline):
     def submit(self, image: torch.Tensor, depth_gt: torch.Tensor, first_image_id: int = 0, object_features=None, object_xywh_list=None) -> None:
         """Enqueue one validation step (image [B, 3, H, W] as captured, ground truth [B, 1, H', W']) on the next slot's stream;
         returns at once.  ``object_features`` / ``object_xywh_list``: the objects of the 2B images [batch | mirrored batch] for a
-        graph with ``object_capacity`` (default: the model's provider is asked, on the slot's stream)."""
+        graph with ``object_capacity`` (default: the model's provider is asked, on the slot's stream).  ``object_features`` may be an
+        ``objects.Detections`` when the model's provider is a ``DeviceObjectProvider``: its one launch writes the slot's static
+        buffers on the slot's stream (of the batch alone with the provider's ``mirror_width`` set, else of all 2B images)."""
         if tuple(image.shape[1:]) != tuple(self.graphs[0].static_image.shape[1:]) or image.shape[0] != self.B:
             raise ValueError(f"captured for images {(self.B,) + tuple(self.graphs[0].static_image.shape[1:])}, got {tuple(image.shape)}")
         self._submit(image, [image, depth_gt], depth_gt, first_image_id, (object_features, object_xywh_list))
