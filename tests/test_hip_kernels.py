@@ -979,7 +979,8 @@ def test_pointwise_nhwc_split_pinned_tile_shapes(ops, cfg, B, H, W, Cin, Cout, a
 def test_pointwise_nhwc_split_k_across_workgroups(ops, B, H, W, Cin, Cout, act, use_gate, use_res, split):
     """Round 4: a tiny batch's late 1x1 layers share the K slabs of a tile out over several workgroups (raw partial tiles in the
     caller's scratch + a fixed-order finish pass with bias / activation / residual): against fp64, bitwise reproducible, and the
-    scratch query says where it applies."""
+    scratch query says where it applies.
+    The deterministic form of this check -- every operand and workspace between poisoned guards -- is tests/test_hip_memory_bounds.py."""
     lib = ops._lib.load()
     assert (lib.ocv_pointwise_split_workspace_bytes(B * H * W, Cin, Cout) > 0) == split
     x, w, b = rnd("x", (B, Cin, H, W), 1), rnd("w", (Cout, Cin, 1, 1), 2, 1 / math.sqrt(Cin)), rnd("b", (Cout,), 3, 0.2)
@@ -1227,7 +1228,8 @@ def test_channel_mean_and_se_gate(ops, B, C, H, W, R):
 def test_conv_nhwc_does_not_depend_on_stale_memory(ops):
     """Regression: an earlier pipeline read load-destination registers before the loads had landed and only looked
     right when registers / LDS / recycled allocations happened to hold the same data.  Poison the caching allocator
-    with NaN, then require the FIRST run on freshly recycled memory to be correct."""
+    with NaN, then require the FIRST run on freshly recycled memory to be correct.
+    The deterministic form of this check -- every operand and workspace between poisoned guards -- is tests/test_hip_memory_bounds.py."""
     B, H, W, C1, C2, Cout = 4, 120, 160, 256, 24, 128
     cl = torch.channels_last
     x1, x2 = dev(rnd("x1", (B, C1, H, W), 1)).contiguous(memory_format=cl), dev(rnd("x2", (B, C2, H, W), 2)).contiguous(memory_format=cl)
@@ -1318,7 +1320,8 @@ def test_conv_nhwc_split_in_and_out(ops, B, H, W, Cin, Cout, k, act):
 def test_conv3x3_winograd43_split(ops, B, H, W, Cin, Cout, act):
     """ocv_conv3x3_winograd43_split_fwd (F(4x4, 3x3): input transform, 36 batched two-term-fp16 GEMMs on filters scaled out of
     fp16's subnormals, output transform) against an fp64 convolution at the SAME bar as the direct kernel (2e-5 of max |y|),
-    and against the direct kernel itself."""
+    and against the direct kernel itself.
+    The deterministic form of this check -- every operand and workspace between poisoned guards -- is tests/test_hip_memory_bounds.py."""
     x = rnd("x", (B, Cin, H, W), 1)
     w, b = rnd("w", (Cout, Cin, 3, 3), 3, 1 / math.sqrt(Cin * 9)), rnd("b", (Cout,), 4, 0.2)
     if B * H * W * Cout > 4e6:                                  # the full-size case: reference on the GPU in fp64
