@@ -473,7 +473,7 @@ int ocv_se_gate_fwd(const float* mean, const float* w1, const float* b1, const f
 
 /* Convolution k x k (k in {1,3}), stride 1, zero "same" padding, on NHWC fp32 activations, computed as an implicit
  * GEMM on the bf16 matrix cores with split-bf16 operands (x = hi + lo, 3 MFMAs per product, fp32 accumulate;
- * ~1e-6 relative error, see csrc/conv_igemm.hip):
+ * ~1e-6 relative error, see csrc/conv_igemm.hip; shared pieces csrc/conv_tile.hpp):
  *   y[b][h][w][co] = act( bias[co] + sum_{ky,kx,ci} xcat[b][h+ky-k/2][w+kx-k/2][ci] * Wt[ky*k+kx][co][ci] ) (+ residual)
  * xcat is x1 [B,H,W,C1] followed along channels by the optional x2 [B,H,W,C2] (virtual concat: the skip connection of
  * UpSampleWithSkip, modules/DenseFeatureExtractor.py:44-47).  w_hi / w_lo: bf16 [k*k][Cout][Cp], Cp = C1+C2 rounded up

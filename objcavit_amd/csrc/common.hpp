@@ -42,7 +42,20 @@ __device__ __forceinline__ float fast_silu(float x) { return x * fast_sigmoid(x)
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-// Two-term split of an fp32 value into the 2-byte (hi, lo) bit patterns of the "hl32" activation layout (csrc/conv_igemm.hip):
+// XCD-aware, bijective workgroup map.  The hardware deals workgroup ids round-robin over the eight XCDs (id & 7); this
+// returns the position of workgroup ``wg`` of ``nwg`` in an order in which each XCD owns one contiguous run of positions,
+// so that neighbouring tiles (a pixel tile's N-tiles, adjacent halos) meet in the same L2.
+__device__ __forceinline__ int ocv_xcd_remap(int wg, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// COUNTED wait: the wave's N newest vector-memory operations may stay in flight (__syncthreads() would emit vmcnt(0)).
+// Only for operations without a register destination (LDS-DMA): see gload16 in conv_tile.hpp for why never otherwise.
+template <int N>
+__device__ __forceinline__ void ocv_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// Two-term split of an fp32 value into the 2-byte (hi, lo) bit patterns of the "hl32" activation layout (csrc/conv_tile.hpp):
 // F16 = fp16 terms (hi = fp16(v), lo = fp16(v - hi): 22 bits down to an absolute floor of 2^-25, range +-65504 -- beyond it inf,
 // loud), else bf16 terms (16 bits, fp32's range).  Which one a tensor holds is the producing call's ``f16`` flag; consumers are
 // told the same flag.

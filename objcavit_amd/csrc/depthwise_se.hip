@@ -58,10 +58,7 @@ __global__ __launch_bounds__(256, 2) void dw_slide_kernel(DWSArgs p) {
   int tile, chunk;
   long b;
   {
-    const int nwg = gridDim.x;
-    int wg = blockIdx.x;
-    const int qq = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
+    const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
     tile = wg % p.tiles;
     const int rest = wg / p.tiles;
     chunk = rest % p.chunks;
@@ -278,10 +275,7 @@ __global__ __launch_bounds__(dwr_threads(S), dwr_waves_per_simd(S)) void dw_rows
   int tile, chunk;
   long b;
   {                                                           // XCD-aware, as dw_slide_kernel
-    const int nwg = gridDim.x;
-    int wg = blockIdx.x;
-    const int qq = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
+    const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
     tile = wg % p.tiles;
     const int rest = wg / p.tiles;
     chunk = rest % p.chunks;

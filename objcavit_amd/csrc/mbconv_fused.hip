@@ -77,11 +77,7 @@ __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_exp
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // scalar: what depends on it branches on the scalar unit
 
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
   const int tile = wg / p.nchunks, chunk = wg - tile * p.nchunks;
   const int b = tile / p.tiles_per_image, t2 = tile - b * p.tiles_per_image;
   const int ty = t2 / p.tiles_x, tx = t2 - ty * p.tiles_x;

@@ -21,8 +21,10 @@
 // matrix pipe.  Partial sums go to one workspace slab per K-slice; a second
 // tiny kernel adds the slabs in fixed order (bitwise reproducible, no float
 // atomics) together with bias and the positional embedding -> tokens [B, S, E].
-#include "common.hpp"
-#include "../../include/objcavit_hip.h"
+//
+// Second half of the file: the same embedding on a PRE-SPLIT feature map (ocv_patch_embed_split_fwd), as GEMMs of the
+// convolutions' LDS-DMA kernel (conv_dma.hip, launched through ocv_conv_launch).
+#include "conv_tile.hpp"
 
 namespace {
 
@@ -207,5 +209,113 @@ extern "C" int ocv_patch_embed_fwd(const float* fmap, int channels_last, const f
   hipLaunchKernelGGL(patch_embed_reduce_kernel, dim3(ocv_cdiv(n4, 256)), dim3(256), 0, st, a.part, ks, (long)a.M,
                      a.gh * a.gw, bias, pos, pos_bs, out);
   OCV_CHECK_LAUNCH("ocv_patch_embed_fwd(reduce)");
+  return 0;
+}
+
+// =====================================================================================================================
+// Patch embedding (Conv2d(C -> E, kernel = stride = 16) + flatten + bias + positional embedding; modules/ObjCAViT.py:287-288,
+// 333,362-364, modules/layers.py:11-12,17-22) on a PRE-SPLIT feature map, as 16 split-bf16 GEMMs in ONE launch of the DMA
+// kernel.  In the hl32 layout the 16 pixels x C channels of one patch row are 16 C consecutive "channels" (C a multiple of
+// 32: whole hi|lo blocks), and the patches of one image row follow each other without a gap: for a fixed ky the feature map
+// IS the row-major operand of a 1 x 1 GEMM over a (B gh) x gw pixel grid with 16 C channels whose grid rows lie 16 image rows
+// apart (ConvArgs::rowpitch) and whose first row is image row ky (the batch offset xz_bytes).  The 16 raw results
+// [ky][B S][E] are summed in a fixed order with bias and positional embedding by patch_sum_kernel.
+// Products as everywhere in the convolutions: hi*hi + hi*lo + lo*hi, error <= 2^-17 per product, fp32 accumulation.
+// =====================================================================================================================
+namespace {
+__global__ __launch_bounds__(256) void patch_sum_kernel(const float* __restrict__ part, long M, int E, int S,
+                                                        const float* __restrict__ bias, const float* __restrict__ pos,
+                                                        long pos_bs, float* __restrict__ out, int nslab) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;     // float4 index
+  const int e4 = E / 4;
+  if (idx >= M * e4) return;
+  const long m = idx / e4;
+  const int e = (int)(idx - m * e4) * 4;
+  // K pieces in a FIXED order: four interleaved chains (pieces k = j mod 4), eight loads in flight, then (a0 + a1) + (a2 + a3)
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+  const float* src = part + m * E + e;
+  const long slab = M * E;
+  int k = 0;
+  for (; k + 8 <= nslab; k += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const f32x4*>(src + (k + j) * slab);
+    a0 += v[0]; a1 += v[1]; a2 += v[2]; a3 += v[3];
+    a0 += v[4]; a1 += v[5]; a2 += v[6]; a3 += v[7];
+  }
+  for (; k < nslab; ++k) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + k * slab);
+    if ((k & 3) == 0) a0 += v; else if ((k & 3) == 1) a1 += v; else if ((k & 3) == 2) a2 += v; else a3 += v;
+  }
+  f32x4 a = (a0 + a1) + (a2 + a3);
+  if (bias != nullptr) a += *reinterpret_cast<const f32x4*>(bias + e);
+  if (pos != nullptr) {
+    const long b = m / S, s = m - b * S;
+    a += *reinterpret_cast<const f32x4*>(pos + b * pos_bs + s * E + e);
+  }
+  *reinterpret_cast<f32x4*>(out + m * E + e) = a;
+}
+}  // namespace
+
+namespace {
+// K parts of the patch embedding.  Per patch the contraction is over (ky, kx, c): 16 C / 32 K steps for each of the 16 patch rows,
+// 1024 steps at C = 128, which the kernel walks as ONE axis (ConvArgs::zflat) cut in `parts` equal pieces -- one workgroup per (row
+// tile, piece), raw partial slabs summed in a fixed order by patch_sum_kernel.  With the pieces = the 16 patch rows (rounds 2 - 4) bs
+// 16 was 19 x 16 = 304 workgroups: two rounds of the 256 CUs for 1.19 rounds of work (203 us); 13 pieces are 247 workgroups, ONE round
+// of 79 steps.  The part count is the one with the least modelled time: rounds x (steps x ~1.4 us + ~6 us of prologue and stores) + the
+// slabs written and read back at ~3 TB/s; at least 16 steps per piece.
+int patch_parts(int B, int C, int h, int w, int E) {
+  const long M = (long)B * (h / 16) * (w / 16);
+  const long tiles = (long)ocv_cdiv(M, CBM) * ocv_cdiv(E, CBN);
+  const int S = 16 * (16 * C / CBK);
+  int best = 1;
+  double cost = 0.0;
+  for (int n = 1; n <= 256 && S / n >= 16; ++n) {
+    const double c = (double)((tiles * n + 255) / 256) * (1.4 * ((S + n - 1) / n) + 6.0) + (double)n * (double)M * E * 8.0 / 3.0e6;
+    if (n == 1 || c < cost) { cost = c; best = n; }
+  }
+  return best;
+}
+}  // namespace
+
+extern "C" size_t ocv_patch_embed_split_workspace_bytes(int B, int C, int h, int w, int E) {
+  if (B < 1 || C < 32 || C % 32 != 0 || h < 16 || w < 16 || E < 8 || E % 8 != 0) return 0;
+  return (size_t)patch_parts(B, C, h, w, E) * B * (h / 16) * (w / 16) * E * sizeof(float);
+}
+
+extern "C" int ocv_patch_embed_split_fwd(const void* x_hl, int C, const void* w_hi, const void* w_lo, const float* oscale, int f16,
+                                         const float* bias, const float* pos, long pos_bs, float* out, int B, int h, int w, int E,
+                                         void* workspace, size_t workspace_bytes, ocv_stream_t stream) {
+  OCV_CHECK_ARG(x_hl && w_hi && w_lo && out && workspace, "ocv_patch_embed_split_fwd: null pointer");
+  OCV_CHECK_ARG(f16 == 0 || f16 == 1, "ocv_patch_embed_split_fwd: f16 must be 0 (bf16 pairs) or 1 (fp16 pairs)");
+  const size_t need = ocv_patch_embed_split_workspace_bytes(B, C, h, w, E);
+  OCV_CHECK_ARG(need != 0, "ocv_patch_embed_split_fwd: needs C a multiple of 32 (got %d), E a multiple of 8 (got %d), a map of at "
+                "least one 16 x 16 patch (got %d x %d)", C, E, h, w);
+  OCV_CHECK_ARG(workspace_bytes >= need, "ocv_patch_embed_split_fwd: workspace too small");
+  OCV_CHECK_ARG((reinterpret_cast<uintptr_t>(x_hl) & 127) == 0 && ocv_aligned16(w_hi) && ocv_aligned16(w_lo) && ocv_aligned16(bias) &&
+                    ocv_aligned16(pos) && ocv_aligned16(out) && ocv_aligned16(workspace) && (pos == nullptr || pos_bs % 4 == 0),
+                "ocv_patch_embed_split_fwd: x_hl must be 128-byte aligned, the rest 16-byte aligned");
+  OCV_CHECK_ARG((long)B * h * w * C * 4 < (1L << 32) && (long)E * 16 * C * 2 < (1L << 32),
+                "ocv_patch_embed_split_fwd: each operand must be smaller than 4 GiB");
+  const int gh = h / 16, gw = w / 16;
+  ConvArgs a{};
+  a.xhl = (const __bf16*)x_hl; a.whi = (const __bf16*)w_hi; a.wlo = (const __bf16*)w_lo; a.y = (float*)workspace;
+  a.C1 = 16 * C; a.Cin = 16 * C; a.Cout = E; a.H = B * gh; a.W = gw; a.ks = 1; a.act = OCV_ACT_NONE;
+  a.ksplit = 1;
+  a.zflat = patch_parts(B, C, h, w, E);                                       // pieces of the (ky, kx, c) axis: slab k at workspace + k M E
+  a.Cpo = (E + 31) / 32 * 32;
+  a.f16 = f16; a.oscale = oscale;                                             // (the 16 GEMMs share their output channels' scales)
+  a.zbatch = 16;
+  a.xz_bytes = (long)w * 2 * C * (long)sizeof(__bf16);                        // one image row down
+  a.wz_bytes = (long)E * 16 * C * (long)sizeof(__bf16);
+  a.rowpitch = (unsigned)(16L * w * 2 * C * (long)sizeof(__bf16));           // grid rows: 16 image rows apart
+  // image b's rows start at image row b h, not b gh 16, when h is not a multiple of 16: only then is the grid not uniform
+  OCV_CHECK_ARG(h % 16 == 0 || B == 1, "ocv_patch_embed_split_fwd: the map height must be a multiple of 16 for B > 1 (got %d)", h);
+  const int rc = ocv_conv_launch(a, 1, (hipStream_t)stream);
+  if (rc != 0) return rc;
+  const long M = (long)B * gh * gw;
+  hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)((M * (E / 4) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const float*)workspace, M, E, gh * gw, bias, pos, pos_bs, out, a.zflat);
+  OCV_CHECK_LAUNCH("ocv_patch_embed_split_fwd(sum)");
   return 0;
 }

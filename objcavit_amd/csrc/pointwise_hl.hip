@@ -144,10 +144,7 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
   // resident and streams rows; row-block major otherwise: rows read once, all of W resident)
   int bx, by;
   {
-    const int nwg = gridDim.x;
-    int wg = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
     if (p.col_major) { by = wg / p.nbx; bx = wg % p.nbx; }
     else { bx = wg / p.nby; by = wg % p.nby; }
   }
@@ -180,24 +177,22 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + i * 1024), 16, 0, 0);
       }
     };
-#define OCV_PH_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
     // slabs 0 .. NBUF - 2 up front; in interval it (consumers on slab it) slab it + NBUF - 1 goes into the buffer slab
     // it - 1 has just left, then only slab it + 1 is waited for: (NBUF - 2) slabs of pieces may stay in flight
     const int pro = min(NBUF - 1, nslab);
     for (int it = 0; it < pro; ++it) issue(it);
-    if (pro == NBUF - 1) OCV_PH_WAIT_VM((NBUF - 2) * PIECES);
-    else OCV_PH_WAIT_VM(0);
+    if (pro == NBUF - 1) ocv_wait_vm<(NBUF - 2) * PIECES>();
+    else ocv_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     for (int it = 0; it < nslab; ++it) {
       if (it + NBUF - 1 < nslab) {
         issue(it + NBUF - 1);
-        OCV_PH_WAIT_VM((NBUF - 2) * PIECES);
+        ocv_wait_vm<(NBUF - 2) * PIECES>();
       } else {
-        OCV_PH_WAIT_VM(0);
+        ocv_wait_vm<0>();
       }
       __builtin_amdgcn_s_barrier();
     }
-#undef OCV_PH_WAIT_VM
     return;
   }
 

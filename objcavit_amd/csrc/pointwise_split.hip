@@ -251,10 +251,7 @@ __global__ __launch_bounds__(64 * WN * WK) void pw_tile_kernel(PSArgs p) {
   // rows; row-block major otherwise, so its rows are read once and all of W stays resident).
   int bx, by, kz = 0;
   {
-    const int nwg = gridDim.x;
-    int wg = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
     if (p.ksplit > 1) {                                     // K slice fastest: the slices of a tile run side by side
       kz = wg % p.ksplit;
       wg /= p.ksplit;

@@ -111,11 +111,7 @@ template <int NJ>
 __global__ __launch_bounds__(320, 4) void tap_interp_kernel(TIArgs p) {
   extern __shared__ __attribute__((aligned(16))) float zs[];          // [NBUF][fq_cap][CB]
   const int tid = threadIdx.x;
-  int wg = blockIdx.x;
-  {                                                    // XCD-aware: the eight L2s each take a contiguous run of tiles (shared halos)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);   // XCD-aware: the eight L2s each take a contiguous run of tiles (shared halos)
   const int tx = wg % p.tiles_x;
   wg /= p.tiles_x;
   const int ty = wg % p.tiles_y, b = wg / p.tiles_y;

@@ -2,7 +2,7 @@
 // NHWC, for the UNet decoder on gfx950 (UpSampleWithSkip.forward, modules/DenseFeatureExtractor.py:44-47:
 // F.interpolate(x, size=skip.size, mode='bilinear', align_corners=True); torch.cat([up_x, skip], dim=1)).
 //
-// Output format = what the split-bf16 convolution consumes directly (csrc/conv_igemm.hip): the "hl32" layout of
+// Output format = what the split-bf16 convolution consumes directly (csrc/conv_tile.hpp): the "hl32" layout of
 // include/objcavit_hip.h -- per pixel and per block of 32 channels of the concatenated activation [B, H, W, C1 + C2],
 // 32 hi = bf16(v) values followed by the 32 lo = bf16(v - hi) values (one 128-byte line per convolution K step; pad
 // channels up to the next multiple of 32 are written as zeros).  Producing the split ONCE here
@@ -35,7 +35,7 @@ namespace {
 
 struct UpArgs {
   const float *x, *skip;
-  unsigned short* hl;           // bf16 bit patterns, hl32 layout (csrc/conv_igemm.hip): per pixel and 32-channel block, 32 hi then 32 lo
+  unsigned short* hl;           // bf16 bit patterns, hl32 layout (csrc/conv_tile.hpp): per pixel and 32-channel block, 32 hi then 32 lo
   int Cp;                       // channels rounded up to 32 (pad channels are written as zeros)
   int h, w, H, W, C1, C2;
   float sh, sw;
@@ -71,11 +71,7 @@ __global__ __launch_bounds__(256) void upsample_concat_split_kernel(UpArgs p) {
   // bilinear taps of neighbouring output pixels re-read the same low-resolution rows -- through their XCD's own L2.
   // Each XCD gets a contiguous band of output rows (FETCH_SIZE of the 240 x 320 launch was 3x the algorithmic bytes
   // with the plain grid-stride order); a workgroup walks UP_ITEMS consecutive 256-element groups.
-  long wg = blockIdx.x;
-  {
-    const long nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, i = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
+  const long wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
   const long idx0 = wg * (256L * UP_ITEMS) + threadIdx.x;
 #pragma unroll 1
   for (int it = 0; it < UP_ITEMS; ++it) {
@@ -142,11 +138,7 @@ constexpr int UP8_ITEMS = 4;          // items per thread, all loaded before the
 template <bool F16>
 __global__ __launch_bounds__(256) void upsample_concat_split8_kernel(Up8Args p) {
   const int C = p.C1 + p.C2;
-  long wg = blockIdx.x;
-  {
-    const long nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, i = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
+  const long wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
   const long pix0 = wg * p.PB;                                   // wave-uniform: scalar divisions, once per workgroup
   const int X0 = (int)(pix0 % p.W);
   const long t0 = pix0 / p.W;
@@ -225,11 +217,7 @@ __device__ __forceinline__ float4 up_sel(bool second, const float4 a, const floa
 template <bool F16>
 __global__ __launch_bounds__(256) void upsample_concat_split_2x2_kernel(UpBArgs p) {
   const int C = p.C1 + p.C2;
-  long wg = blockIdx.x;
-  {
-    const long nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, i = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
+  const long wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
   const long blk0 = wg * p.PB;                                   // wave-uniform
   const int bx0 = (int)(blk0 % p.BW);
   const long t0 = blk0 / p.BW;
@@ -356,11 +344,7 @@ template <bool F16>
 __global__ __launch_bounds__(256) void upsample_concat_split_lds_kernel(UpLArgs p) {
   __shared__ __attribute__((aligned(16))) float4 src[ULS_H * ULS_W][ULC / 4];
   const int tid = threadIdx.x;
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, i = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
+  const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
   const long b = wg / p.tiles_per_image;
   const int t2 = wg - (int)b * p.tiles_per_image;
   const int ty = t2 / p.tiles_x, tx = t2 - ty * p.tiles_x;

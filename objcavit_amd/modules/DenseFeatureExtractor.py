@@ -177,7 +177,7 @@ class SplitConv3x3:
         B, Cin, H, W = x.shape
         if self.conv.kernel_size[0] == 3 and hip_ops.winograd_pays(B, H, W, Cin, self.conv.out_channels):
             # the deep stages: Winograd F(4x4, 3x3), 4x fewer matrix-core operations; fp16 pairs inside whatever the input's
-            # element type (every tile scaled by a power of two from its own maximum: fp32's range) -- csrc/conv_igemm.hip
+            # element type (every tile scaled by a power of two from its own maximum: fp32's range) -- csrc/conv_winograd.hip
             if self._wino is None:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("weight preparation during graph capture: run one eager warm-up call first")

@@ -21,7 +21,7 @@ that lies in no guarded payload, ``g.check()`` (also run at exit) compares every
 ``g.never_written(t)`` counts the 32-bit words of an output that still hold the pattern.
 
 guard_bytes.  The default, 1 MiB, is twice the largest store one mis-masked tile of the dense kernels can make in the table of
-tests/test_hip_memory_bounds.py: conv_igemm's tile is 256 output rows, a row of at most 512 fp32 channels is 2 KiB,
+tests/test_hip_memory_bounds.py: the convolutions' tile (csrc/conv_tile.hpp CBM) is 256 output rows, a row of at most 512 fp32 channels is 2 KiB,
 256 x 512 x 4 B = 512 KiB (an hl32 row costs the same 4 B per channel: 2 x 2 B x ceil32(C)).  A table row whose output is wider
 passes a larger figure (the dense split-K row writes 1032 channels: 8 MiB).  A stray store that flies further than the guard
 lands in another arena's guard or in memory nobody owns; the first is reported against that arena, the second is not seen.

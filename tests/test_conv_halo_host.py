@@ -1,4 +1,4 @@
-"""-m "not gpu": the host side of the halo-staged 3 x 3 kernel (conv_halo_dma_kernel, csrc/conv_igemm.hip) -- the new symbols,
+"""-m "not gpu": the host side of the halo-staged 3 x 3 kernel (conv_halo_dma_kernel, csrc/conv_dma.hip) -- the new symbols,
 ocv_conv3x3_halo_supported over a grid of shapes (against the stated rule and against the library's own split-K query), the LDS bytes
 its launch requests, and the dispatch setter's argument check."""
 import os

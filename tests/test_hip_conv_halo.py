@@ -1,4 +1,4 @@
-"""The halo-staged dense 3 x 3 kernel (conv_halo_dma_kernel, csrc/conv_igemm.hip: one 8 x 32 pixel patch per workgroup, the
+"""The halo-staged dense 3 x 3 kernel (conv_halo_dma_kernel, csrc/conv_dma.hip: one 8 x 32 pixel patch per workgroup, the
 (8 + 2) x (32 + 2) halo patch of a 32-channel chunk staged once) against the tap ring it stands beside (conv_split_dma_kernel),
 switched by ocv_conv3x3_set_dispatch in one process on the same operands: same products, same accumulation order, so the fp32
 output and the hl32 split output are compared with torch.equal.  Shapes are the smallest at which the staging can go wrong:

@@ -1308,6 +1308,44 @@ def test_conv_nhwc_split_in_and_out(ops, B, H, W, Cin, Cout, k, act):
     assert rel_dev(y, y3) < 1e-5
 
 
+@pytest.mark.parametrize("f16", [False, True], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("k", [1, 3])
+def test_conv_nhwc_split_ragged_tile_elementwise_split_out(ops, k, f16):
+    """The tap ring's element-wise epilogue (Cout % 8 != 0; conv_store_elems, csrc/conv_tile.hpp) on a ragged last tile
+    (M = 297 = 256 + 41 rows) with everything it can do at once: per-channel scale, bias, LeakyReLU, residual, the fp32 and
+    the split output.  Against float64 on the operands the kernel read (x = hi + lo of the split input) at the decoder's
+    bars; the split copy is the pair of the fp32 result, its pad channels zero, and rows past M are not written."""
+    from decoder_shadow import BF16_TOL, F16_TOL
+    B, H, W, Cin, Cout = 1, 9, 33, 40, 12
+    lib = ops._lib.load()
+    x32 = dev(rnd("x", (B, Cin, H, W), 21)).contiguous(memory_format=torch.channels_last)
+    w32 = rnd("w", (Cout, Cin, k, k), 22, 1 / math.sqrt(Cin * k * k))
+    bias, res = dev(rnd("b", (Cout,), 23, 0.3)), dev(rnd("r", (B, H, W, Cout), 24))
+    xs = ops.split_act(x32, f16=f16)
+    w_hi, w_lo, osc = (ops.prep_conv_weight(dev(w32), f16=f16) + (None,))[:3]
+    M = B * H * W
+    ybuf = torch.full((M + 256, Cout), float("nan"), device="cuda")          # room for a whole second tile behind the result
+    ys = ops.SplitAct.empty(B, Cout, H, W, "cuda", f16=f16)
+    ys.hl.view(torch.int16).fill_(0x7E7E)
+    p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    rc = lib.ocv_conv_nhwc_split_x_fwd(xs.hl.data_ptr(), Cin, w_hi.data_ptr(), w_lo.data_ptr(), p(osc), int(f16), p(bias), p(res),
+                                       ybuf.data_ptr(), ys.hl.data_ptr(), B, H, W, Cout, k, ops.ACT_LEAKY_RELU, None, 0,
+                                       torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.ocv_last_error().decode(errors="replace")
+    torch.cuda.synchronize()
+    assert torch.isnan(ybuf[M:]).all()                                       # the ragged tile's 215 missing rows
+    y = ybuf[:M].view(B, H, W, Cout).permute(0, 3, 1, 2)
+    hi, lo = xs.parts()
+    ref = F.leaky_relu(F.conv2d(hi.double().cpu() + lo.double().cpu(), w32.double(), bias.double().cpu(), padding=k // 2), 0.01)
+    ref = ref + res.double().cpu().permute(0, 3, 1, 2)
+    err, bar = rel_dev(y.cpu().double(), ref), F16_TOL if f16 else BF16_TOL
+    print(f"ragged element-wise split-out k={k} {'fp16' if f16 else 'bf16'} pairs: {err:.3g} (bar {bar:.1e})")
+    assert err < bar
+    assert rel_dev(ys.float(), y) < (1e-6 if f16 else 1e-5)                  # a 22- / 16-bit pair of the fp32 result
+    pads = ys.hl.view(B, H, W, 1, 2, 32)[..., Cout:]
+    assert not bool(pads.view(torch.int16).any())
+
+
 @pytest.mark.parametrize("B,H,W,Cin,Cout,act", [
     (2, 30, 40, 96, 64, 2),        # H not a multiple of 4 (last tile row half outside), LeakyReLU
     (1, 7, 9, 40, 72, 0),          # odd H and W, Cin % 32 != 0, Cout % 32 != 0

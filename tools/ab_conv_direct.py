@@ -1,7 +1,7 @@
 """(needs tools/diag/conv_direct.patch.txt applied: the direct form is not in the product -- profiles/r06_conv_direct.txt)
 Round 6: the pre-split convolution / GEMM kernel's two routes on the decoder's launches, same process, alternating.
   route 0  conv_split_dma_kernel: accumulators parked in LDS, all eight wavefronts store, one tile per workgroup (rounds 2 - 5)
-  route 1  the shipped rule (csrc/conv_igemm.hip launch_conv): conv_split_direct_kernel -- operands swapped, in-register epilogue, a
+  route 1  the shipped rule (then launch_conv of csrc/conv_igemm.hip, today ocv_conv_launch of csrc/conv_dma.hip): conv_split_direct_kernel -- operands swapped, in-register epilogue, a
            workgroup walks npn = 2 or 3 channel tiles -- where that is modelled to pay, route 0 elsewhere; npnK = direct form forced
 `python tools/ab_conv_direct.py [bs] [iters]` -> a table of us per launch (HIP events over `iters` back-to-back launches, three blocks per
 route interleaved, best block) + whether the two routes' outputs are bit-identical, + an npn sweep on the multi-tile launches.

@@ -1,5 +1,5 @@
 """The five dense 3 x 3 launches of one bs-16 480 x 640 step (four 128 -> 128 at 240 x 320, one 256 -> 256 at 120 x 160; fp16 pairs,
-bias + LeakyReLU, split output) under both kernels of csrc/conv_igemm.hip, switched by ocv_conv3x3_set_dispatch in one process
+bias + LeakyReLU, split output) under both kernels of csrc/conv_dma.hip, switched by ocv_conv3x3_set_dispatch in one process
 (1 = tap ring, conv_split_dma_kernel; 2 = halo-staged, conv_halo_dma_kernel; 0 = automatic): time per launch (20 launches after
 3), the sum over the five, and a SHA-1 of the output bytes, so that two library builds (OCV_LIB_PATH: a parent build exports the
 setter as a no-op and runs the ring under every mode) can be compared bit for bit from their logs.

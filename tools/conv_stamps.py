@@ -1,4 +1,4 @@
-"""Diagnostic: per-phase cycle shares of conv_igemm (needs a build with OCV_EXTRA_HIPCC_FLAGS=-DOCV_STAMPS)."""
+"""Diagnostic: per-phase cycle shares of conv_igemm_kernel / conv_split_dma_kernel (csrc/conv_igemm.hip, csrc/conv_dma.hip; needs a build with OCV_EXTRA_HIPCC_FLAGS=-DOCV_STAMPS)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,7 +12,7 @@ hi, lo = hip_ops.prep_conv_weight(torch.randn(Cout, C1 + C2, 3, 3, device="cuda"
 for _ in range(3): hip_ops.conv_nhwc(x1, x2, hi, lo, None, 3, 2)
 torch.cuda.synchronize()
 out = (ctypes.c_ulonglong * 16)()
-fn = lib.ocv_conv_read_stamps; fn.restype = ctypes.c_int
+fn = lib.ocv_conv_igemm_read_stamps; fn.restype = ctypes.c_int
 print("rc", fn(out))
 v = list(out)
 n = max(v[7], 1)
