@@ -23,7 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.hpp"
+#include "token_tile.hpp"
 #include "../../include/objcavit_hip.h"
 
 namespace {
@@ -175,21 +175,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs p) {
 // fp16's range applies to q / sqrt(d), k and v (beyond +-65504 the affected rows turn inf / NaN); ocv_attention_set_dispatch(1)
 // selects the exact kernel above.
 // ---------------------------------------------------------------------------
-typedef _Float16 at_h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 at_h16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void at_split(float x, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)x;
-  lo = (_Float16)((x - (float)hi) * 2048.0f);
-}
-
-__device__ __forceinline__ void at_mfma3(const at_h16x8 ah, const at_h16x8 al, const at_h16x8 bh, const at_h16x8 bl, f32x16& a1,
-                                         f32x16& a2) {
-  a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, a2, 0, 0, 0);
-  a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, a2, 0, 0, 0);
-  a1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, a1, 0, 0, 0);
-}
-
+// (the split, its product step and the typedefs: csrc/token_tile.hpp; staging and fragment order are this kernel's own)
 template <bool VEC>
 __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -202,14 +188,13 @@ __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
   const int h = blockIdx.y, b = blockIdx.z;
   const int qbase = (blockIdx.x * 4 + wave) * 32;
   const float NEG_INF = -__builtin_inff();
-  constexpr float LO_DOWN = 1.0f / 2048.0f;
 
   const float* qp = p.q + (long)b * p.q_bs + h * HD;
   const float* kp = p.k + (long)b * p.k_bs + h * HD;
   const float* vp = p.v + (long)b * p.v_bs + h * HD;
 
   // Q^T fragments (B operand): lane (query l31, half hh) of step t holds Q[query][16 t + 8 hh + e] * scale * log2(e)
-  at_h16x8 qh[2], ql[2];
+  h16x8 qh[2], ql[2];
   {
     const int qi = qbase + l31;
     const bool ok = qi < p.Sq;
@@ -220,7 +205,7 @@ __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         _Float16 a, c;
-        at_split(ok ? src[16 * t + e] * sc : 0.f, a, c);
+        split_h2(ok ? src[16 * t + e] * sc : 0.f, a, c);
         qh[t][e] = a;
         ql[t][e] = c;
       }
@@ -251,17 +236,17 @@ __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
       const int tile = r >> 5, kk = r & 31;
       {
         const float f[4] = {kv.x, kv.y, kv.z, kv.w};
-        at_h16x4 a, c;
+        h16x4 a, c;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           _Float16 x, y;
-          at_split(f[j], x, y);
+          split_h2(f[j], x, y);
           a[j] = x;
           c[j] = y;
         }
         _Float16* d = Kf + ((long)((tile * 2 + (d4 >> 4)) * 2) * 64 + ((d4 >> 3) & 1) * 32 + kk) * 8 + (d4 & 7);
-        *reinterpret_cast<at_h16x4*>(d) = a;
-        *reinterpret_cast<at_h16x4*>(d + 512) = c;
+        *reinterpret_cast<h16x4*>(d) = a;
+        *reinterpret_cast<h16x4*>(d + 512) = c;
       }
       {
         const float f[4] = {vv.x, vv.y, vv.z, vv.w};
@@ -271,7 +256,7 @@ __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           _Float16 x, y;
-          at_split(f[j], x, y);
+          split_h2(f[j], x, y);
           d[8 * j] = x;
           d[8 * j + 512] = y;
         }
@@ -291,7 +276,7 @@ __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
       f32x16 s1 = {0}, s2 = {0}, s;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
-        at_mfma3(*reinterpret_cast<const at_h16x8*>(kf + t * 1024), *reinterpret_cast<const at_h16x8*>(kf + t * 1024 + 512), qh[t], ql[t], s1, s2);
+        mfma3(*reinterpret_cast<const h16x8*>(kf + t * 1024), *reinterpret_cast<const h16x8*>(kf + t * 1024 + 512), qh[t], ql[t], s1, s2);
       float tmax = NEG_INF;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -319,20 +304,20 @@ __global__ __launch_bounds__(256) void attention_h2_kernel(AttnArgs p) {
         }
       }
       // ---- O^T += V^T . P^T: the probabilities' register order is the k-slot order of the B operand
-      at_h16x8 ph[2], pl[2];
+      h16x8 ph[2], pl[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           _Float16 a, c;
-          at_split(s[8 * t + e], a, c);
+          split_h2(s[8 * t + e], a, c);
           ph[t][e] = a;
           pl[t][e] = c;
         }
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t)
-        at_mfma3(*reinterpret_cast<const at_h16x8*>(vf + t * 1024), *reinterpret_cast<const at_h16x8*>(vf + t * 1024 + 512), ph[t], pl[t], o1, o2);
+        mfma3(*reinterpret_cast<const h16x8*>(vf + t * 1024), *reinterpret_cast<const h16x8*>(vf + t * 1024 + 512), ph[t], pl[t], o1, o2);
     }
   }
 

@@ -21,7 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.hpp"
+#include "token_tile.hpp"
 #include "../../include/objcavit_hip.h"
 
 namespace {
@@ -348,15 +348,16 @@ __global__ __launch_bounds__(512, 2) void bin_head_split3_kernel(const float* __
 // in a second launch) and every bin tile costs 24 MFMAs instead of 48.  fp16's range: a map value or folded weight beyond
 // +-65504 turns the pixel's depth inf / NaN; OCV_BINHEAD=split3 / exact keep fp32's range.
 // ---------------------------------------------------------------------------
-typedef _Float16 bh_h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void bh_split8_h2(const float4 u, const float4 v, bh_h16x8& hi, bh_h16x8& lo) {
+// h16x8, LO_UP and LO_DOWN come from csrc/token_tile.hpp.  NOT its split8_h2 and mfma3: bin_head_h2_kernel's instruction slots are
+// pinned (sched_group_barrier), and through split8_h2 -- the same conversions, the insertions in another order -- both
+// <false, *> instances come out in a different order; the product step below issues hi hi between the two small terms.
+__device__ __forceinline__ void bh_split8_h2(const float4 u, const float4 v, h16x8& hi, h16x8& lo) {
   const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const _Float16 h = (_Float16)f[i];
     hi[i] = h;
-    lo[i] = (_Float16)((f[i] - (float)h) * 2048.0f);
+    lo[i] = (_Float16)((f[i] - (float)h) * LO_UP);
   }
 }
 
@@ -424,7 +425,7 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
   }
   for (int idx = tid; idx < NB * CH / 8; idx += 512) {
     const int k = idx >> 4, o = idx & 15;                    // bin, K octet
-    bh_h16x8 hi, lo;
+    h16x8 hi, lo;
     float4 u = ld4(wb + (long)k * CH + 8 * o), v = ld4(wb + (long)k * CH + 8 * o + 4);
     u.x *= LOG2E; u.y *= LOG2E; u.z *= LOG2E; u.w *= LOG2E;
     v.x *= LOG2E; v.y *= LOG2E; v.z *= LOG2E; v.w *= LOG2E;
@@ -436,8 +437,8 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
     }
     bh_split8_h2(u, v, hi, lo);
     _Float16* d = wfrag + ((((k >> 5) * 8 + (o >> 1)) * 2) * 64 + (o & 1) * 32 + (k & 31)) * 8;
-    *reinterpret_cast<bh_h16x8*>(d) = hi;
-    *reinterpret_cast<bh_h16x8*>(d + 512) = lo;
+    *reinterpret_cast<h16x8*>(d) = hi;
+    *reinterpret_cast<h16x8*>(d + 512) = lo;
   }
   if (tid < NB) {
     bl[tid] = bout[tid] * LOG2E;
@@ -460,18 +461,18 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
   for (; tile < ntiles; tile += gridDim.x) {
     const long pix = (long)tile * TP3 + wave * 32 + l31;
     const int tn = tile + gridDim.x;
-    bh_h16x8 ph[8], pl[8];
+    h16x8 ph[8], pl[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) bh_split8_h2(cur[2 * s], cur[2 * s + 1], ph[s], pl[s]);
     __builtin_amdgcn_sched_barrier(0);                       // (the raw values are dead before the next tile's are asked for)
     if (tn < ntiles) load_px(nxt, (long)tn * TP3 + wave * 32 + l31);
 
     // weight fragments of (bin tile t, K step s): hi at wfrag + ((t 8 + s) 2) 512 + lane 8, lo' 512 halves further
-    bh_h16x8 wh[3], wl[3];                                   // three rotating sets: K step s lives in set s % 3
+    h16x8 wh[3], wl[3];                                   // three rotating sets: K step s lives in set s % 3
     auto fetch_w = [&](int t, int s_) {
       const _Float16* wf = wfrag + ((t * 8 + s_) * 2) * 512 + lane * 8;
-      wh[s_ % 3] = *reinterpret_cast<const bh_h16x8*>(wf);
-      wl[s_ % 3] = *reinterpret_cast<const bh_h16x8*>(wf + 512);
+      wh[s_ % 3] = *reinterpret_cast<const h16x8*>(wf);
+      wl[s_ % 3] = *reinterpret_cast<const h16x8*>(wf + 512);
     };
     auto fetch_bias = [&](int t, f32x16& a1) {               // accumulator register r = bin acc_row(r, hh): four runs of four
       const float* bp = bl + t * 32 + 4 * hh;
@@ -503,7 +504,7 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
       bh_f32x2 lg[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i)
-        lg[i] = bh_f32x2{a2[2 * i], a2[2 * i + 1]} * (1.0f / 2048.0f) + bh_f32x2{a1[2 * i], a1[2 * i + 1]};
+        lg[i] = bh_f32x2{a2[2 * i], a2[2 * i + 1]} * LO_DOWN + bh_f32x2{a1[2 * i], a1[2 * i + 1]};
       fetch_bias(tb, a1);
       float tmax = fmaxf(lg[0].x, lg[0].y);
 #pragma unroll
@@ -570,8 +571,8 @@ __global__ __launch_bounds__(512, 2) void bin_head_h2_kernel(const float* __rest
         for (int r = 2; r < 16; r += 2) m = fmaxf(fmaxf(m, a1[r]), a1[r + 1]);
         return m;
       };
-      bh_h16x8 wq[6];
-      auto fetch_q = [&](int j) { wq[j % 6] = *reinterpret_cast<const bh_h16x8*>(wfrag + (j * 2) * 512 + lane * 8); };
+      h16x8 wq[6];
+      auto fetch_q = [&](int j) { wq[j % 6] = *reinterpret_cast<const h16x8*>(wfrag + (j * 2) * 512 + lane * 8); };
       float tmx[NB / 32];
 #pragma unroll
       for (int j = 0; j < 6; ++j) fetch_q(j);

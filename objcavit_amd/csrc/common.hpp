@@ -51,7 +51,8 @@ __device__ __forceinline__ int ocv_xcd_remap(int wg, int nwg) {
 }
 
 // COUNTED wait: the wave's N newest vector-memory operations may stay in flight (__syncthreads() would emit vmcnt(0)).
-// Only for operations without a register destination (LDS-DMA): see gload16 in conv_tile.hpp for why never otherwise.
+// Only for operations without a register destination: LDS-DMA (see gload16 in conv_tile.hpp for why never otherwise), and N = 0 behind
+// stores or a fence, to drain them before a ticket is drawn (csrc/token_h2.hip).
 template <int N>
 __device__ __forceinline__ void ocv_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -138,7 +139,7 @@ int ocv_cross_attn_fused_launch(const float* q_src, const float* k_src, const fl
                                 const float* in_w, const float* in_b, const float* out_w, const float* out_b, float* out, int B,
                                 int Sq, int Sk, int Se, int E, int H, hipStream_t st);
 
-// the same on packed three-term-split weights, K / V projected once per image into kv_ws [B][2][32][128] (csrc/token_split3.hip)
+// the same on packed three-term-split weights, K / V projected once per image into kv_ws [B][2][32][128] (csrc/xattn_split3.hip)
 int ocv_cross_attn_split3_launch(const float* q_src, const float* k_src, const float* v_src, const uint8_t* mask, int mask_ld,
                                  const void* in_p3, const float* in_b, const void* out_p3, const float* out_b, float* out,
                                  float* kv_ws, int B, int Sq, int Sk, int Se, int E, int H, hipStream_t st);
@@ -148,6 +149,9 @@ int ocv_ffn_split_count(int M, int FF);
 int ocv_ffn_split_launch(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                          const float* gamma, const float* beta, float eps, const uint8_t* zero_row_mask, float* out, int M,
                          int FF, float* part, int nsplit, hipStream_t st);
+// its finish pass alone, out = LayerNorm(x + sum_s part[s] + b2), on partials [nsplit][M][128] written by another file's kernel
+int ocv_ffn_finish_launch(const char* name, const float* x, const float* b2, const float* gamma, const float* beta, float eps,
+                          const uint8_t* zero_row_mask, float* out, int M, const float* part, int nsplit, hipStream_t st);
 
 // A caller's ocv_encoder_layer_params (element ``index`` of an array whose stride is the caller's struct_size) copied into
 // the library's own struct: fields beyond the caller's struct_size read as NULL.  false = struct_size too small to hold

@@ -11,7 +11,7 @@
 // layers, by launch latency.
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "token_tile.hpp"
 #include "../../include/objcavit_hip.h"
 
 namespace {
@@ -237,26 +237,7 @@ __device__ __forceinline__ void load_wregs(float4 (&w)[FKC / 8], const float* __
     w[t] = (8 * t < kc) ? ld4(wrow + 8 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// residual + LayerNorm over the 128 columns of a 32-row tile held in Cs (one wavefront per 8 rows)
-__device__ __forceinline__ void ln_rows(const float (*Cs)[BN + 1], const float* gamma, const float* beta, float eps,
-                                        const uint8_t* zero_mask, float* out, int ldo, int m0, int M, int lane, int wave) {
-  const float g0 = gamma[lane], g1 = gamma[lane + 64];
-  const float b0 = beta[lane], b1 = beta[lane + 64];
-#pragma unroll
-  for (int i = 0; i < FM / 4; ++i) {
-    const int row = wave * (FM / 4) + i, m = m0 + row;
-    const float x0 = Cs[row][lane], x1 = Cs[row][lane + 64];
-    const float mean = wave_sum(x0 + x1) * (1.0f / BN);
-    const float d0 = x0 - mean, d1 = x1 - mean;
-    const float var = wave_sum(d0 * d0 + d1 * d1) * (1.0f / BN);
-    const float rstd = 1.0f / sqrtf(var + eps);
-    if (m < M) {
-      const bool z = zero_mask != nullptr && zero_mask[m] != 0;
-      out[(long)m * ldo + lane] = z ? 0.f : d0 * rstd * g0 + b0;
-      out[(long)m * ldo + lane + 64] = z ? 0.f : d1 * rstd * g1 + b1;
-    }
-  }
-}
+static_assert(BN == E128 && FM == TM, "ln_rows (token_tile.hpp) works on this file's 32 x 128 tiles");
 
 template <int EPI>
 __global__ __launch_bounds__(256) void linear_stream_kernel(LinearArgs p) {
@@ -605,6 +586,16 @@ int ocv_ffn_split_launch(const float* x, const float* w1, const float* b1, const
   OCV_CHECK_LAUNCH("ocv_ffn_split_launch");
   hipLaunchKernelGGL(ffn_finish_kernel, dim3(ocv_cdiv(M, FM)), dim3(256), 0, st, a);
   OCV_CHECK_LAUNCH("ocv_ffn_split_launch(finish)");
+  return 0;
+}
+
+// the finish pass alone, for the split FFNs of other files on the same partial layout (csrc/token_split3.hip): a kernel can be
+// launched only from the object that holds it.  ``name``: the caller's label for a launch error.
+int ocv_ffn_finish_launch(const char* name, const float* x, const float* b2, const float* gamma, const float* beta, float eps,
+                          const uint8_t* zero_row_mask, float* out, int M, const float* part, int nsplit, hipStream_t st) {
+  FFNArgs a{x, nullptr, nullptr, nullptr, b2, gamma, beta, eps, zero_row_mask, out, M, 0, const_cast<float*>(part), nsplit};
+  hipLaunchKernelGGL(ffn_finish_kernel, dim3(ocv_cdiv(M, FM)), dim3(256), 0, st, a);
+  OCV_CHECK_LAUNCH(name);
   return 0;
 }
 

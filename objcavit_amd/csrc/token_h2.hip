@@ -11,117 +11,14 @@
 // number of workgroups).  LDS 51 KB instead of 69.
 // fp16's range applies to the tokens, the hidden activations and the weights (packer saturates); OCV_TOKENS=split3 keeps
 // the three-term bf16 kernels, OCV_TOKENS=fp32 the exact ones.
+// The split, the staging, the resident fragments, their contraction and the tile LayerNorm are csrc/token_tile.hpp.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "token_tile.hpp"
 #include "../../include/objcavit_hip.h"
 
 namespace {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int TM = 32;               // tokens per workgroup
-constexpr int E128 = 128;
-constexpr int KC = 128;              // hidden units per feed-forward chunk
-constexpr int NS = E128 / 16;        // K steps of a 128-long contraction
-constexpr int PROW = E128 + 8;       // fp16 per plane row (272 bytes)
-constexpr int PLANE = TM * PROW;
-constexpr float LO_UP = 2048.0f, LO_DOWN = 1.0f / 2048.0f;
-
-__device__ __forceinline__ void split_h2(float x, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)x;
-  lo = (_Float16)((x - (float)hi) * LO_UP);
-}
-
-__device__ __forceinline__ void split8_h2(const float4 u, const float4 v, h16x8& h, h16x8& l) {
-  const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    _Float16 a, c;
-    split_h2(f[i], a, c);
-    h[i] = a;
-    l[i] = c;
-  }
-}
-
-// rows [m0, m0 + 32) of a row-major [M][128] fp32 matrix -> two fp16 planes (rows >= M: zeros)
-__device__ __forceinline__ void stage_rows(_Float16* planes, const float* __restrict__ src, int m0, int M, int tid) {
-  const int row = tid >> 3;
-  const bool ok = m0 + row < M;
-  const float* s = src + (long)(ok ? m0 + row : 0) * E128;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int o = (tid & 7) + 8 * i;
-    float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
-    if (ok) {
-      u = ld4(s + 8 * o);
-      v = ld4(s + 8 * o + 4);
-    }
-    h16x8 h, l;
-    split8_h2(u, v, h, l);
-    _Float16* d = planes + row * PROW + 8 * o;
-    *reinterpret_cast<h16x8*>(d) = h;
-    *reinterpret_cast<h16x8*>(d + PLANE) = l;
-  }
-}
-
-// the 32 x 128 fp32 tile in Cs -> two fp16 planes
-__device__ __forceinline__ void tile_to_planes(_Float16* planes, const float (*Cs)[E128 + 1], int tid) {
-  const int row = tid >> 3;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int o = (tid & 7) + 8 * i;
-    const float* c = &Cs[row][8 * o];
-    h16x8 h, l;
-    split8_h2(make_float4(c[0], c[1], c[2], c[3]), make_float4(c[4], c[5], c[6], c[7]), h, l);
-    _Float16* d = planes + row * PROW + 8 * o;
-    *reinterpret_cast<h16x8*>(d) = h;
-    *reinterpret_cast<h16x8*>(d + PLANE) = l;
-  }
-}
-
-// eight K steps of one 32-row weight tile: 8 x 2 parts x 16 bytes per lane = 64 VGPRs
-struct WFragH { h16x8 w[NS][2]; };
-
-__device__ __forceinline__ void load_wh(WFragH& f, const _Float16* wp) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) f.w[s][p] = *reinterpret_cast<const h16x8*>(wp + (long)s * 1024 + p * 512);
-  }
-}
-
-// (a1, a2) += planes[32 x 128] . (fragments)^T : rows = tokens, columns = the tile's 32 outputs
-__device__ __forceinline__ void chunk_h2(f32x16& a1, f32x16& a2, const _Float16* planes, const WFragH& f, int l31, int hh) {
-  const _Float16* pa = planes + l31 * PROW + 8 * hh;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const h16x8 ah = *reinterpret_cast<const h16x8*>(pa + 16 * s);
-    const h16x8 al = *reinterpret_cast<const h16x8*>(pa + 16 * s + PLANE);
-    a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, f.w[s][0], a2, 0, 0, 0);
-    a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, f.w[s][1], a2, 0, 0, 0);
-    a1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, f.w[s][0], a1, 0, 0, 0);
-  }
-}
-
-// LayerNorm of the 32 x 128 tile in Cs, in place (one wavefront per 8 rows)
-__device__ __forceinline__ void ln_tile_inplace(float (*Cs)[E128 + 1], const float* gamma, const float* beta, float eps, int lane,
-                                                int wave) {
-  const float g0 = gamma[lane], g1 = gamma[lane + 64];
-  const float b0 = beta[lane], b1 = beta[lane + 64];
-#pragma unroll 4
-  for (int i = 0; i < TM / 4; ++i) {
-    const int row = wave * (TM / 4) + i;
-    const float x0 = Cs[row][lane], x1 = Cs[row][lane + 64];
-    const float mean = wave_sum(x0 + x1) * (1.0f / E128);
-    const float d0 = x0 - mean, d1 = x1 - mean;
-    const float var = wave_sum(d0 * d0 + d1 * d1) * (1.0f / E128);
-    const float rstd = 1.0f / sqrtf(var + eps);
-    Cs[row][lane] = d0 * rstd * g0 + b0;
-    Cs[row][lane + 64] = d1 * rstd * g1 + b1;
-  }
-}
 
 struct TailArgs {
   const float *ctx, *x;                 // [M][128]
@@ -167,11 +64,11 @@ __global__ __launch_bounds__(256, 1) void layer_tail_h2_kernel(TailArgs p) {
   load_wh(fa, p.wo_p + ((long)wave * NS * 2) * 512 + lane * 8);
   load_wh(fb, w1_at(0));                // W1 chunk 0 and W2 chunk 0: in flight under the output projection and LN1
   load_wh(fc, w2_at(0));
-  stage_rows(xp, p.ctx, m0, p.M, tid);
+  stage_rows_h2(xp, p.ctx, m0, p.M, tid);
   __syncthreads();
   {
     f32x16 a1 = {0}, a2 = {0};
-    chunk_h2(a1, a2, xp, fa, l31, hh);
+    project_s(xp, fa, l31, hh, a1, a2);
     if (nchunk > 1) load_wh(fa, w1_at(1));
     const float bo = p.bo[col];
 #pragma unroll
@@ -183,7 +80,7 @@ __global__ __launch_bounds__(256, 1) void layer_tail_h2_kernel(TailArgs p) {
   __syncthreads();
   ln_tile_inplace(Cs, p.g1, p.be1, p.eps, lane, wave);
   __syncthreads();
-  tile_to_planes(xp, Cs, tid);                        // every wavefront is past its reads of the ctx planes
+  tile_to_planes_h2(xp, Cs, tid);                        // every wavefront is past its reads of the ctx planes
   __syncthreads();
 
   // ---- x2 = LN2(x1 + W2 relu(W1 x1 + b1) + b2).  Chunk c: phase 1 multiplies by W1(c), phase 2 by W2(c).
@@ -193,7 +90,7 @@ __global__ __launch_bounds__(256, 1) void layer_tail_h2_kernel(TailArgs p) {
   auto ffn_chunk = [&](int c, WFragH& s1, WFragH& s2, WFragH& s3) {
     const float b1 = p.b1[(c0 + c) * KC + col];
     f32x16 h1 = {0}, h2 = {0};
-    chunk_h2(h1, h2, xp, s1, l31, hh);
+    project_s(xp, s1, l31, hh, h1, h2);
     if (c + 1 < nchunk) load_wh(s1, w2_at(c + 1));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -204,7 +101,7 @@ __global__ __launch_bounds__(256, 1) void layer_tail_h2_kernel(TailArgs p) {
       d[PLANE] = b;
     }
     __syncthreads();
-    chunk_h2(acc1, acc2, hp, s2, l31, hh);
+    project_s(hp, s2, l31, hh, acc1, acc2);
     if (c + 2 < nchunk) load_wh(s2, w1_at(c + 2));
     __syncthreads();
     (void)s3;
@@ -225,14 +122,14 @@ __global__ __launch_bounds__(256, 1) void layer_tail_h2_kernel(TailArgs p) {
     float* mine = p.part + ((long)(blk * G + g) * TM) * E128 + col;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ocv_store_sc1(mine + acc_row(r, hh) * E128, acc1[r] + acc2[r] * LO_DOWN);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ocv_wait_vm<0>();
     __syncthreads();
     if (tid == 0) {
       const unsigned old = __hip_atomic_fetch_add((ocv_gu32*)(p.cnt + blk), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const bool last = old == (unsigned)(G - 1);
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ocv_wait_vm<0>();
         __hip_atomic_store((ocv_gu32*)(p.cnt + blk), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // nobody else touches it any more
       }
       last_flag = last ? 1u : 0u;
@@ -285,13 +182,13 @@ __global__ __launch_bounds__(256, 1) void layer_tail_h2_kernel(TailArgs p) {
   if (!next) return;
 
   // ---- the next layer's packed projection: wavefront w -> channel tiles 3 w .. 3 w + 2 of the 12
-  tile_to_planes(xp, Cs, tid);
+  tile_to_planes_h2(xp, Cs, tid);
   __syncthreads();
   auto qkv_tile = [&](int t, const WFragH& f) {
     const int n = (wave * 3 + t) * 32 + l31;
     const float bn = p.bqkv[n];
     f32x16 a1 = {0}, a2 = {0};
-    chunk_h2(a1, a2, xp, f, l31, hh);
+    project_s(xp, f, l31, hh, a1, a2);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + acc_row(r, hh);
@@ -335,17 +232,13 @@ extern "C" int ocv_layer_tail_h2_ws_fwd(const float* ctx, const float* x, const 
                                         const void* next_in_proj_h2, const float* next_in_proj_b, float eps,
                                         const uint8_t* zero_row_mask, float* out, float* qkv_next, int M, int E, int FF,
                                         void* workspace, size_t workspace_bytes, ocv_stream_t stream) {
-  OCV_CHECK_ARG(ctx && x && p_caller && out, "ocv_layer_tail_h2_fwd: null pointer");
   ocv_encoder_layer_params pv;
-  OCV_CHECK_ARG(ocv_layer_params_view(p_caller, 0, &pv), "ocv_layer_tail_h2_fwd: params->struct_size (%zu) is not a valid ocv_encoder_layer_params size", p_caller->struct_size);
+  if (ocv_layer_tail_check("ocv_layer_tail_h2_fwd", "h2", ctx, x, p_caller,
+                           [](const ocv_encoder_layer_params& v) { return v.out_proj_h2 && v.linear1_h2 && v.linear2_h2; },
+                           "needs the packed two-term fp16 weights (ocv_pack_split_h2_fwd)", next_in_proj_h2, next_in_proj_b, zero_row_mask, out,
+                           qkv_next, E, FF, &pv) != 0)
+    return -1;
   const ocv_encoder_layer_params* p = &pv;
-  OCV_CHECK_ARG(p->out_proj_h2 && p->linear1_h2 && p->linear2_h2, "ocv_layer_tail_h2_fwd: needs the packed two-term fp16 weights (ocv_pack_split_h2_fwd)");
-  OCV_CHECK_ARG(E == E128 && FF >= KC && FF % KC == 0, "ocv_layer_tail_h2_fwd: needs E = %d and FF a multiple of %d (got %d, %d)", E128, KC, E, FF);
-  OCV_CHECK_ARG((next_in_proj_h2 == nullptr) == (qkv_next == nullptr) && (next_in_proj_h2 == nullptr || next_in_proj_b != nullptr),
-                "ocv_layer_tail_h2_fwd: next_in_proj_h2 / next_in_proj_b / qkv_next go together");
-  // (the kernel projects the LN2 tile it holds, not the zeroed rows it stores: only the last layer of a stack is masked, and it has no next)
-  OCV_CHECK_ARG(zero_row_mask == nullptr || qkv_next == nullptr,
-                "ocv_layer_tail_h2_fwd: zero_row_mask together with a next projection (qkv_next) is not supported");
   OCV_CHECK_ARG(M >= 0&& ocv_aligned16(ctx) && ocv_aligned16(x) && ocv_aligned16(out) && ocv_aligned16(qkv_next) &&
                     ocv_aligned16(p->out_proj_h2) && ocv_aligned16(p->linear1_h2) && ocv_aligned16(p->linear2_h2) && ocv_aligned16(next_in_proj_h2),
                 "ocv_layer_tail_h2_fwd: bad M / alignment");

@@ -33,131 +33,16 @@
 //                         MFMAs once registers 8 t .. 8 t + 7 are packed as step t --, scores^T = K Q^T, softmax over the
 //                         keys (rows: in-lane + one xor-32 shuffle), context^T = V^T P^T, context rows to LDS as two fp16
 //                         planes, output projection transposed (a register quad = 16 contiguous bytes of an output row).
+// (split_h2, mfma3, WFragH, stage_rows_h2 / rows_load + rows_store, project_t and pack_steps: csrc/token_tile.hpp; the weight packer:
+// csrc/token_pack.hip)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "token_tile.hpp"
 #include "../../include/objcavit_hip.h"
 
 namespace {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TM = 32;               // queries per sub-tile
-constexpr int E128 = 128;
-constexpr int NS = E128 / 16;        // K steps of a 128-long contraction
-constexpr int PROW = E128 + 8;       // fp16 per plane row (272 bytes: b128 reads of 32 rows are conflict-free)
-constexpr int PLANE = TM * PROW;
-constexpr float LO_UP = 2048.0f, LO_DOWN = 1.0f / 2048.0f;
-constexpr float H_MAX = 65504.0f;
-
-__device__ __forceinline__ void split_h2(float x, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)x;
-  lo = (_Float16)((x - (float)hi) * LO_UP);
-}
-
-__device__ __forceinline__ void split8_h2(const float4 u, const float4 v, h16x8& h, h16x8& l) {
-  const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    _Float16 a, c;
-    split_h2(f[i], a, c);
-    h[i] = a;
-    l[i] = c;
-  }
-}
-
-// 256 threads stage rows [m0, m0 + 32) of a row-major [*, 128] fp32 matrix as two fp16 planes (rows >= M: zeros)
-__device__ __forceinline__ void stage_rows_h2(_Float16* planes, const float* __restrict__ src, int m0, int M, int tid) {
-  const int row = tid >> 3;
-  const bool ok = m0 + row < M;
-  const float* s = src + (long)(ok ? m0 + row : 0) * E128;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int o = (tid & 7) + 8 * i;                     // octet of the row
-    float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
-    if (ok) {
-      u = ld4(s + 8 * o);
-      v = ld4(s + 8 * o + 4);
-    }
-    h16x8 h, l;
-    split8_h2(u, v, h, l);
-    _Float16* d = planes + row * PROW + 8 * o;
-    *reinterpret_cast<h16x8*>(d) = h;
-    *reinterpret_cast<h16x8*>(d + PLANE) = l;
-  }
-}
-
-// one product block step: small terms into acc2 (carries 2^-11), the hi hi term into acc1
-__device__ __forceinline__ void mfma3(const h16x8 ah, const h16x8 al, const h16x8 bh, const h16x8 bl, f32x16& acc1, f32x16& acc2) {
-  acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc2, 0, 0, 0);
-  acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc2, 0, 0, 0);
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1, 0, 0, 0);
-}
-
-// the weight fragments of one 32-row tile over the whole 128-long contraction: 8 steps x 2 parts x 16 bytes per lane = 64 VGPRs
-struct WFragH { h16x8 w[NS][2]; };
-
-__device__ __forceinline__ void load_wh(WFragH& f, const _Float16* wp) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) f.w[s][p] = *reinterpret_cast<const h16x8*>(wp + (long)s * 1024 + p * 512);
-  }
-}
-
-// D^T[n][m] = sum_k W[n][k] X[m][k]: weight fragments = A operand, plane rows = B operand.  FENCE: a scheduling barrier every
-// two steps keeps the compiler from hoisting all sixteen LDS reads (64 registers) above the MFMAs (the 128-VGPR pre-pass).
-template <bool FENCE = false>
-__device__ __forceinline__ void project_t(const WFragH& f, const _Float16* planes, int l31, int hh, f32x16& a1, f32x16& a2) {
-  const _Float16* pb = planes + l31 * PROW + 8 * hh;
-#pragma unroll
-  for (int st = 0; st < NS; ++st) {
-    const h16x8 xh = *reinterpret_cast<const h16x8*>(pb + 16 * st);
-    const h16x8 xl = *reinterpret_cast<const h16x8*>(pb + 16 * st + PLANE);
-    mfma3(f.w[st][0], f.w[st][1], xh, xl, a1, a2);
-    if (FENCE && (st & 1)) __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// registers 8 t .. 8 t + 7 of an accumulator-shaped value -> the two fp16 parts of k-step t of an MFMA operand
-__device__ __forceinline__ void pack_steps(const f32x16 v, h16x8 (&hi)[2], h16x8 (&lo)[2]) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      _Float16 a, c;
-      split_h2(v[8 * t + e], a, c);
-      hi[t][e] = a;
-      lo[t][e] = c;
-    }
-  }
-}
-
-// W [N][K] fp32 (row stride ldw) -> packed two-term fp16 fragments; one thread per (jt, s, lane)
-__global__ __launch_bounds__(256) void pack_h2_kernel(const float* __restrict__ W, int ldw, int N, int K, _Float16* __restrict__ out,
-                                                      long items) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= items) return;
-  const int lane = (int)(i & 63);
-  const long js = i >> 6;
-  const int nsteps = (K + 15) >> 4;
-  const int s = (int)(js % nsteps), jt = (int)(js / nsteps);
-  const int n = jt * 32 + (lane & 31), k0 = 16 * s + 8 * (lane >> 5);
-  float f[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float w = (n < N && k0 + e < K) ? W[(long)n * ldw + k0 + e] : 0.f;
-    f[e] = fabsf(w) > H_MAX ? copysignf(H_MAX, w) : w;                 // saturate; a NaN fails the comparison and stays a NaN
-  }
-  h16x8 h, l;
-  split8_h2(make_float4(f[0], f[1], f[2], f[3]), make_float4(f[4], f[5], f[6], f[7]), h, l);
-  _Float16* d = out + (js * 2) * 512 + lane * 8;
-  *reinterpret_cast<h16x8*>(d) = h;
-  *reinterpret_cast<h16x8*>(d + 512) = l;
-}
 
 struct XKVArgs {
   const float *k_src, *v_src;          // [B][Sk][128]
@@ -166,38 +51,6 @@ struct XKVArgs {
   _Float16* kv;                        // [B][2][4][64][2][2][8]
   int Sk, Se;
 };
-
-// the two halves of stage_rows_h2: global loads into registers (issued early), split + LDS stores (after the previous
-// image's MFMAs have read the planes)
-struct RowRegs { float4 u[2], v[2]; };
-
-__device__ __forceinline__ void rows_load(RowRegs& r, const float* __restrict__ src, int M, int tid) {
-  const int row = tid >> 3;
-  const bool ok = row < M;
-  const float* s = src + (long)(ok ? row : 0) * E128;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int o = (tid & 7) + 8 * i;
-    r.u[i] = r.v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ok) {
-      r.u[i] = ld4(s + 8 * o);
-      r.v[i] = ld4(s + 8 * o + 4);
-    }
-  }
-}
-
-__device__ __forceinline__ void rows_store(_Float16* planes, const RowRegs& r, int tid) {
-  const int row = tid >> 3;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int o = (tid & 7) + 8 * i;
-    h16x8 h, l;
-    split8_h2(r.u[i], r.v[i], h, l);
-    _Float16* d = planes + row * PROW + 8 * o;
-    *reinterpret_cast<h16x8*>(d) = h;
-    *reinterpret_cast<h16x8*>(d + PLANE) = l;
-  }
-}
 
 // One workgroup per operand (blockIdx.y) walks images blockIdx.x, + gridDim.x, ... on ONE load of its weight fragments: a
 // workgroup per image re-read 64 KB of fragments for 16 KB of rows and the launch ran at the L2's pace (13 us at bs 512, 45 us
@@ -225,12 +78,13 @@ __global__ __launch_bounds__(256, 3) void xattn_kv_h2_kernel(XKVArgs p, int B) {
     if (!is_v) {
       project_t<true>(f, planes, l31, hh, a1, a2);                                      // K^T: rows d, columns keys
     } else {
+      // V: rows keys, columns d.  project_s<true>, written out: through the helper this kernel takes 4 more VGPRs and orders its LDS reads differently
       const _Float16* pa = planes + l31 * PROW + 8 * hh;
 #pragma unroll
       for (int st = 0; st < NS; ++st) {
         const h16x8 xh = *reinterpret_cast<const h16x8*>(pa + 16 * st);
         const h16x8 xl = *reinterpret_cast<const h16x8*>(pa + 16 * st + PLANE);
-        mfma3(xh, xl, f.w[st][0], f.w[st][1], a1, a2);                                  // V: rows keys, columns d
+        mfma3(xh, xl, f.w[st][0], f.w[st][1], a1, a2);
         if (st & 1) __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -338,7 +192,7 @@ __global__ __launch_bounds__(256, OWNKV ? 2 : 3) void xattn_main_h2_kernel(XAArg
     load_wh(fq, p.in_h2 + ((long)(8 + h) * NS * 2) * 512 + lane * 8);              // Wv rows of head h
     {
       f32x16 a1 = {0}, a2 = {0}, a;
-      const _Float16* pa = planes + (NSUB + 1) * 2 * PLANE + l31 * PROW + 8 * hh;
+      const _Float16* pa = planes + (NSUB + 1) * 2 * PLANE + l31 * PROW + 8 * hh;      // (written out as in xattn_kv_h2_kernel: the two agree bit for bit)
 #pragma unroll
       for (int st = 0; st < NS; ++st) {
         const h16x8 xh = *reinterpret_cast<const h16x8*>(pa + 16 * st);
@@ -451,22 +305,6 @@ int g_one_launch_wgs = 320;          // one launch up to here (measured: 14.9 / 
 
 extern "C" int ocv_mha_few_keys_h2_set_dispatch(int one_launch_max_workgroups) {
   g_one_launch_wgs = one_launch_max_workgroups < 0 ? 320 : one_launch_max_workgroups;
-  return 0;
-}
-
-extern "C" size_t ocv_split_h2_packed_elems(int N, int K) {
-  if (N < 1 || K < 1) return 0;
-  return (size_t)((N + 31) / 32) * ((K + 15) / 16) * 2 * 512;
-}
-
-extern "C" int ocv_pack_split_h2_fwd(const float* W, int ldw, int N, int K, void* packed, ocv_stream_t stream) {
-  OCV_CHECK_ARG(W && packed, "ocv_pack_split_h2_fwd: null pointer");
-  OCV_CHECK_ARG(N >= 1 && K >= 1 && ldw >= K, "ocv_pack_split_h2_fwd: bad sizes N=%d K=%d ldw=%d", N, K, ldw);
-  OCV_CHECK_ARG(ocv_aligned16(packed), "ocv_pack_split_h2_fwd: packed must be 16-byte aligned");
-  const long items = (long)((N + 31) / 32) * ((K + 15) / 16) * 64;
-  hipLaunchKernelGGL(pack_h2_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, ldw, N, K,
-                     (_Float16*)packed, items);
-  OCV_CHECK_LAUNCH("ocv_pack_split_h2_fwd");
   return 0;
 }
 

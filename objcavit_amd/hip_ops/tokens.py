@@ -1,5 +1,5 @@
 """hip_ops: linear / LayerNorm / attention / multi-head attention / transformer encoder layers (csrc/linear.hip, attention.hip,
-token_split3.hip, token_h2.hip, xattn_h2.hip).
+token_split3.hip, xattn_split3.hip, token_h2.hip, xattn_h2.hip, token_pack.hip; shared device pieces in token_tile.hpp).
 """
 from __future__ import annotations
 
@@ -193,26 +193,14 @@ def mha(q_src: torch.Tensor, k_src: torch.Tensor, v_src: torch.Tensor, in_proj_w
     few = 0 < (kv_limit if 0 < kv_limit < Sk else Sk) <= 32 and (kv_limit == 0 or m is not None)
     small = few and form == "fp32"
     if packed is not None and token_split3_enabled() and E == 128 and n_heads == 4 and few and form == "h2" and B <= 65535:
-        h2 = []
-        for field, w in (("in_proj_h2", in_proj_w), ("out_proj_h2", out_w)):
-            ver = (w.data_ptr(), w._version)
-            hit = packed.get(field)
-            if hit is None or hit[0] != ver:
-                hit = packed[field] = (ver, SplitWeightH2(w))
-            h2.append(hit[1].packed)
+        h2 = [_packed(packed, field, w, SplitWeightH2) for field, w in (("in_proj_h2", in_proj_w), ("out_proj_h2", out_w))]
         with timed(name):                              # the K / V record (32 KB per image) fits the MHA workspace sized above
             check(lib.ocv_mha_few_keys_h2_fwd(q_src.data_ptr(), k_src.data_ptr(), v_src.data_ptr(), _ptr(m), h2[0].data_ptr(),
                                               in_proj_b.data_ptr(), h2[1].data_ptr(), out_b.data_ptr(), out.data_ptr(), B, Sq, Sk,
                                               int(kv_limit), E, n_heads, ws.data_ptr(), ws.numel(), _stream()), "ocv_mha_few_keys_h2_fwd")
         return out
     if packed is not None and token_split3_enabled() and E == 128 and n_heads == 4 and not small:
-        p3 = []
-        for field, w in (("in_proj_p3", in_proj_w), ("out_proj_p3", out_w)):
-            ver = (w.data_ptr(), w._version)
-            hit = packed.get(field)
-            if hit is None or hit[0] != ver:
-                hit = packed[field] = (ver, SplitWeight3(w))
-            p3.append(hit[1].packed)
+        p3 = [_packed(packed, field, w, SplitWeight3) for field, w in (("in_proj_p3", in_proj_w), ("out_proj_p3", out_w))]
         with timed(name):
             check(lib.ocv_mha_split3_fwd(q_src.data_ptr(), k_src.data_ptr(), v_src.data_ptr(), _ptr(m), p3[0].data_ptr(),
                                          in_proj_b.data_ptr(), p3[1].data_ptr(), out_b.data_ptr(), out.data_ptr(), B, Sq, Sk,
@@ -262,6 +250,16 @@ class SplitWeight3:
             raise RuntimeError("weight packing during graph capture: run one eager warm-up call first")
         self.packed = torch.empty(int(lib.ocv_split3_packed_elems(self.n, self.k)), dtype=torch.bfloat16, device=w.device)
         check(lib.ocv_pack_split3_fwd(w.data_ptr(), self.k, self.n, self.k, self.packed.data_ptr(), _stream()), "ocv_pack_split3_fwd")
+
+
+def _packed(cache: dict, field: str, weight: torch.Tensor, cls) -> torch.Tensor:
+    """The packed form (``cls``: SplitWeight3 | SplitWeightH2) of ``weight`` from the caller's cache: cache[field] = ((data_ptr,
+    version), cls object), packed on first use and again whenever the weight's storage or version changed."""
+    ver = (weight.data_ptr(), weight._version)
+    hit = cache.get(field)
+    if hit is None or hit[0] != ver:
+        hit = cache[field] = (ver, cls(weight))
+    return hit[1].packed
 
 
 def linear_split3(x: torch.Tensor, weight: SplitWeight3, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE) -> torch.Tensor:
@@ -337,24 +335,14 @@ def layer_params(layer: torch.nn.Module, packed: Optional[dict] = None) -> Tuple
         keep.append(t)
         setattr(st, field, t.data_ptr())
     if packed is not None:
-        for field, key in _P3_FIELDS:
-            w = sd[key]
-            ver = (w.data_ptr(), w._version)
-            hit = packed.get(field)
-            if hit is None or hit[0] != ver:
-                hit = packed[field] = (ver, SplitWeight3(w))
-            keep.append(hit[1].packed)
-            setattr(st, field, hit[1].packed.data_ptr())
+        forms = [("_p3", SplitWeight3)]
         if token_mode() == "h2":                     # + the two-term fp16 copies: the layer tails run on them
+            forms.append(("_h2", SplitWeightH2))
+        for sfx, cls in forms:
             for field, key in _P3_FIELDS:
-                f2 = field.replace("_p3", "_h2")
-                w = sd[key]
-                ver = (w.data_ptr(), w._version)
-                hit = packed.get(f2)
-                if hit is None or hit[0] != ver:
-                    hit = packed[f2] = (ver, SplitWeightH2(w))
-                keep.append(hit[1].packed)
-                setattr(st, f2, hit[1].packed.data_ptr())
+                t = _packed(packed, field.replace("_p3", sfx), sd[key], cls)
+                keep.append(t)
+                setattr(st, field.replace("_p3", sfx), t.data_ptr())
     return st, keep
 
 

@@ -43,7 +43,7 @@ FLOOR = 2e-7
 SENT = 777.0                 # rows behind M hold this before a call and must hold it afterwards
 H2, EXACT = 4, 2             # margins: two-term fp16 kernels / three-term bf16 and exact-fp32 kernels (module docstring)
 # The three-term tail's x2 at 8, not 2: it measured up to 2.34 x d32 (6.1e-7 against d32 2.6e-7, M = 31) where the two-term fp16
-# tails stay at 1.3 x.  Rounding only, by the kernel's text: mfma6 (csrc/token_split3.hip) adds all six bf16 products of a K step into
+# tails stay at 1.3 x.  Rounding only, by the kernel's text: mfma6 (csrc/token_tile.hpp) adds all six bf16 products of a K step into
 # ONE fp32 accumulator, so the running sum is rounded six times per step -- 384 times over the feed-forward block's 1024 hidden
 # units -- where the two-term kernel keeps hi.hi in an accumulator of its own (once per step) and float32 on the CPU sums in
 # vector lanes; operands (24 bits) and dropped products (2^-27) are below that.  Restating that order of summation in float32 on

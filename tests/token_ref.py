@@ -19,7 +19,7 @@ def plain_matmul(a, w):
 
 
 def split_h2(v):
-    """The two-term fp16 split of csrc/token_h2.hip as float64 tensors: hi = fp16(v), lo' = fp16((v - hi) 2^11), so that
+    """The two-term fp16 split of csrc/token_tile.hpp (split_h2) as float64 tensors: hi = fp16(v), lo' = fp16((v - hi) 2^11), so that
     v ~ hi + 2^-11 lo' to 22 significant bits.  The kernels split fp32 values: v is rounded to float32 first."""
     v32 = v.to(torch.float32)
     hi = v32.to(torch.float16)
