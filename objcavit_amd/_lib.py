@@ -125,6 +125,9 @@ PROTOTYPES = {
                                        C.c_int, C.c_long, _stream]),
     "ocv_depth_ingest_fwd": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, C.c_int, C.c_int,
                                        C.c_int, _stream]),
+    "ocv_frame_resize_supported": (C.c_int, [C.c_int] * 4),
+    "ocv_frame_resize_ingest": (C.c_int, [_u8p, C.c_long, C.c_long] + [C.c_int] * 6 + [_f32p, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p,
+                                          C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, _stream]),
     "ocv_depth_finalize_fwd": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, C.c_void_p, C.c_float,
                                          _u8p, _u8p, C.c_float, C.c_float, C.c_int, _stream]),
     "ocv_depth_finalize_stats_fwd": (C.c_int, [_f32p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_int,

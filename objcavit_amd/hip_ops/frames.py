@@ -1,4 +1,5 @@
-"""hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip), full-resolution depth
+"""hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip; a window of any size
+resized to the model's on the way in: csrc/frame_resize.hip), full-resolution depth
 maps out (csrc/depth_finalize.hip), and what is read out of the final map behind them: per-box statistics (csrc/object_depth.hip), the
 point cloud (csrc/point_cloud.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
@@ -82,6 +83,114 @@ def frame_ingest(frames_u8: torch.Tensor, table: torch.Tensor, top: int = 0, lef
         check(lib.ocv_frame_ingest_fwd(frames_u8.data_ptr(), frame, row, Hs, Ws, int(top), int(left), table.data_ptr(),
                                        out.data_ptr() + 4 * plane * int(out_index), B, H, W, 1 if mirror_too else 0, half * plane,
                                        _stream()), "ocv_frame_ingest_fwd")
+    return out
+
+
+FRAME_RESIZE_MAX_RATIO = 8        # include/objcavit_hip.h: OCV_FRAME_RESIZE_MAX_RATIO, source pixels per output pixel along an axis
+_TAPS = {}                        # (device type, index, Hw, Ww, H, W) -> the device copy of the two tap tables
+_TAPS_KEPT = 64                   # sizes kept: a source of ever-changing window sizes must not grow the cache without bound
+
+
+def resize_taps(n_in: int, n_out: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The tap table of one axis of the antialiased resize ``n_in -> n_out`` (the separable triangle filter with half-pixel centres:
+    torch's ``interpolate(mode="bilinear", antialias=True, align_corners=False)`` in float64; enlarging, plain bilinear) ->
+    (start int32 [n_out], weight fp32 [n_out, K]) on the HOST.  All in float64: s = n_in / n_out, support = max(s, 1); output i has its
+    centre at c = s (i + 0.5) and the taps j = lo .. hi - 1 with lo = max(0, int(c - support + 0.5)), hi = min(n_in, int(c + support +
+    0.5)) (int truncates) and w_j = max(0, 1 - |(j - c + 0.5) / support|) divided by their sum; the weights are rounded to fp32 ONCE.
+    K is the largest tap count; shorter rows are padded with weight 0.  Where a tap falls is decided here and nowhere else: torch's own
+    fp32 path decides it in fp32 and puts a tap on the other side at ratios just above 1 (375 -> 352: 4e-4 off).  Needs no GPU."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_taps: sizes must be >= 1, got {n_in} -> {n_out}")
+    s = n_in / n_out
+    support = max(s, 1.0)
+    inv = 1.0 / support
+    c = s * (torch.arange(n_out, dtype=torch.float64) + 0.5)
+    lo = (c - support + 0.5).trunc().clamp_(min=0).to(torch.int64)
+    hi = (c + support + 0.5).trunc().clamp_(max=n_in).to(torch.int64)
+    K = int((hi - lo).max())
+    j = lo.view(-1, 1) + torch.arange(K, dtype=torch.int64).view(1, -1)
+    w = (1.0 - ((j.to(torch.float64) - c.view(-1, 1) + 0.5) * inv).abs()).clamp_(min=0.0)
+    w = torch.where(j < hi.view(-1, 1), w, torch.zeros((), dtype=torch.float64))
+    w = w / w.sum(1, keepdim=True)
+    return lo.to(torch.int32), w.to(torch.float32)
+
+
+def frame_resize_supported(Hw: int, Ww: int, H: int, W: int) -> bool:
+    """Whether ``frame_resize_ingest`` takes an Hw x Ww window to H x W: it shrinks by at most ``FRAME_RESIZE_MAX_RATIO`` along either
+    axis (any enlargement is served).  Asked of the library (ocv_frame_resize_supported), no launch, no GPU."""
+    return bool(_lib.load().ocv_frame_resize_supported(int(Hw), int(Ww), int(H), int(W)))
+
+
+def frame_resize_taps(device, Hw: int, Ww: int, H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(ystart, yweight, xstart, xweight) of ``Hw x Ww -> H x W`` on ``device``: ``resize_taps`` of both axes, uploaded on the current
+    stream when the size is first seen there and kept (the ``taps`` argument of ``frame_resize_ingest``)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.HipLibraryError(f"frame_resize_taps: {device} is no ROCm GPU (there is no CPU fallback)")
+    index = torch.cuda.current_device() if device.index is None else device.index
+    key = (device.type, index, int(Hw), int(Ww), int(H), int(W))
+    taps = _TAPS.get(key)
+    if taps is None:
+        if len(_TAPS) >= _TAPS_KEPT:
+            _TAPS.clear()
+        taps = _TAPS[key] = tuple(t.to(device) for t in resize_taps(Hw, H) + resize_taps(Ww, W))
+    return taps
+
+
+def frame_resize_ingest(frames_u8: torch.Tensor, table: torch.Tensor, size: Tuple[int, int], top: int = 0, left: int = 0,
+                        window: Optional[Tuple[int, int]] = None, mirror_too: bool = False, out: Optional[torch.Tensor] = None,
+                        out_index: int = 0, taps: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+    """``frame_ingest`` for a window of any size: the ``window`` = (Hw, Ww) pixels at (top, left) of uint8 frames [B, Hs, Ws, 3]
+    (default: the rest of the frame) -> fp32 NCHW at ``size`` = (H, W), the model's, through the antialiased resize of ``resize_taps``
+    applied to the ``table`` values (already normalised).  ``mirror_too``, ``out``, ``out_index``: as ``frame_ingest`` takes them; the
+    mirrored half holds the same values flipped along W.  ``taps``: ``frame_resize_taps``' four device tensors for this window and size
+    (default: made on first use and cached per device and size).  A window that shrinks by more than ``FRAME_RESIZE_MAX_RATIO`` along an
+    axis raises ``ValueError`` before any launch.  One launch (ocv_frame_resize_ingest) on the current stream; within (Ky + Kx + 4) 2^-24
+    max|table| of the float64 statement; a window of ``size`` is bit-equal to ``frame_ingest``.  -> the tensor written."""
+    lib = _lib.load()
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError(f"frame_resize_ingest: bad output size {tuple(size)}")
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.dim() == 4:          # the ratio is judged first: it needs no device
+        Hw, Ww = _window(int(frames_u8.shape[1]), int(frames_u8.shape[2]), int(top), int(left), window, "frame_resize_ingest")
+        if not frame_resize_supported(Hw, Ww, H, W):
+            raise ValueError(f"frame_resize_ingest: a {Hw} x {Ww} window to {H} x {W} shrinks by more than {FRAME_RESIZE_MAX_RATIO} "
+                             "along an axis, the most one launch takes (the filter is never truncated): resize in two steps")
+    B, Hs, Ws, frame, row = _frames_view(frames_u8, "frames_u8", torch.uint8, 3)
+    _req(table, "table")
+    if tuple(table.shape) != (3, 256):
+        raise ValueError(f"frame_resize_ingest: table must be [3, 256], got {tuple(table.shape)}")
+    Hw, Ww = _window(Hs, Ws, int(top), int(left), window, "frame_resize_ingest")
+    if taps is None:
+        taps = frame_resize_taps(frames_u8.device, Hw, Ww, H, W)
+    if len(taps) != 4:
+        raise ValueError("frame_resize_ingest: taps = (ystart, yweight, xstart, xweight)")
+    ys, yw, xs, xw = taps
+    for name, st, wt, n in (("y", ys, yw, H), ("x", xs, xw, W)):
+        _req(st, f"taps: {name}start", torch.int32)
+        _req(wt, f"taps: {name}weight")
+        if tuple(st.shape) != (n,) or wt.dim() != 2 or wt.shape[0] != n or wt.shape[1] < 1:
+            raise ValueError(f"frame_resize_ingest: taps of the {name} axis must be int32 [{n}] and fp32 [{n}, K], got "
+                             f"{tuple(st.shape)} / {tuple(wt.shape)}")
+    if out is None:
+        out = torch.empty((2 * B if mirror_too else B, 3, H, W), dtype=torch.float32, device=frames_u8.device)
+        out_index = 0
+    else:
+        _req(out, "frame_resize_ingest: out")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (3, H, W):
+            raise ValueError(f"frame_resize_ingest: out must be [N, 3, {H}, {W}], got {tuple(out.shape)}")
+    N = int(out.shape[0])
+    half = N // 2 if mirror_too else N
+    if (mirror_too and N % 2) or out_index < 0 or out_index + B > half:
+        raise ValueError(f"frame_resize_ingest: {B} image(s) at index {out_index} do not fit out {tuple(out.shape)}"
+                         f"{' (first half: the second takes the mirrors)' if mirror_too else ''}")
+    plane = 3 * H * W
+    with timed("frame_resize_ingest"):
+        check(lib.ocv_frame_resize_ingest(frames_u8.data_ptr(), frame, row, Hs, Ws, int(top), int(left), Hw, Ww, table.data_ptr(),
+                                          ys.data_ptr(), yw.data_ptr(), int(yw.shape[1]), xs.data_ptr(), xw.data_ptr(), int(xw.shape[1]),
+                                          out.data_ptr() + 4 * plane * int(out_index), B, H, W, 1 if mirror_too else 0, half * plane,
+                                          _stream()), "ocv_frame_resize_ingest")
     return out
 
 
@@ -391,6 +500,7 @@ def depth_unproject(depth: torch.Tensor, K: torch.Tensor, capacity: int, stride:
     return res
 
 
-__all__ = ["frame_ingest", "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics",
+__all__ = ["frame_ingest", "resize_taps", "frame_resize_supported", "frame_resize_taps", "frame_resize_ingest", "FRAME_RESIZE_MAX_RATIO",
+           "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics",
            "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
            "unproject_grid", "UNPROJECT_TILE"]

@@ -58,7 +58,7 @@ class _ObjectsResult(PredictResult):
 
 # what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth, its readout
 # boxes and, for the point cloud, its intrinsics (of the source frames, on the device)
-_Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics"], defaults=(None,))
+_Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics", "size"], defaults=(None, None))     # size: the step's final size (``resize``)
 
 Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
 
@@ -167,6 +167,52 @@ def _window(args, Hs: int, Ws: int, crop) -> Tuple[int, int, int, int]:
     return 0, 0, Hs, Ws
 
 
+def _model_size(resize) -> Optional[Tuple[int, int]]:
+    """The ``resize`` keyword of both predictors: None (the window is the model's input, as it is) or the model's (H, W)."""
+    if resize is None:
+        return None
+    H, W = (int(v) for v in resize)
+    if H < 1 or W < 1:
+        raise ValueError(f"resize: the model's (H, W) must be >= 1, got {tuple(resize)}")
+    return H, W
+
+
+def fit_window(Hs: int, Ws: int, H: int, W: int) -> Tuple[int, int, int, int]:
+    """(top, left, Hw, Ww): the largest centred window of an Hs x Ws frame with the aspect ratio of the model's H x W -- the ``crop`` to
+    pass beside ``resize=(H, W)``.  Integer arithmetic: the frame's full height with Ww = floor(Hs * W / H) when the frame is at least as
+    wide as the model's shape (Ws * H >= Hs * W), else its full width with Hw = floor(Ws * H / W); the cut side is ROUNDED DOWN (the
+    window never leaves the frame; its ratio is off by less than one pixel of that side) and never below 1; top / left =
+    floor(margin / 2), so an odd margin leaves the extra pixel at the bottom / right."""
+    Hs, Ws, H, W = int(Hs), int(Ws), int(H), int(W)
+    if min(Hs, Ws, H, W) < 1:
+        raise ValueError(f"fit_window: sizes must be >= 1, got {Hs} x {Ws} -> {H} x {W}")
+    if Ws * H >= Hs * W:
+        Hw, Ww = Hs, max(1, Hs * W // H)
+    else:
+        Hw, Ww = max(1, Ws * H // W), Ws
+    return (Hs - Hw) // 2, (Ws - Ww) // 2, Hw, Ww
+
+
+def boxes_to_model(xywh, window_size: Tuple[int, int], model_size: Tuple[int, int]):
+    """Detector boxes (centre x, centre y, width, height, ...) in pixels of the WINDOW -> pixels of the model's input, for the model's
+    object provider under ``resize``: cx, w times W / Ww and cy, h times H / Hw; columns beyond the fourth and the <UNK> box
+    (-1, -1, -1, -1) pass through unchanged.  ``xywh``: a tensor [..., >= 4] (-> a new tensor), or a list of such tensors / None (-> a
+    list, None kept).  The boxes of ``boxes=`` (readout, object metrics) are NOT scaled: the final map has the window's size."""
+    if xywh is None:
+        return None
+    if not isinstance(xywh, torch.Tensor):
+        return [boxes_to_model(b, window_size, model_size) for b in xywh]
+    if xywh.dim() < 1 or xywh.shape[-1] < 4:
+        raise ValueError(f"boxes_to_model: expected [..., >= 4] boxes, got {tuple(xywh.shape)}")
+    (Hw, Ww), (H, W) = (int(v) for v in window_size), (int(v) for v in model_size)
+    scale = torch.ones(xywh.shape[-1], dtype=torch.float64)
+    scale[0] = scale[2] = W / Ww
+    scale[1] = scale[3] = H / Hw
+    out = xywh * scale.to(device=xywh.device, dtype=xywh.dtype)
+    unk = (xywh[..., :4] == -1).all(-1, keepdim=True)
+    return torch.where(unk, xywh, out)
+
+
 def _frame_list(frames: Frames, what: str, dims: int) -> List[torch.Tensor]:
     """A batch tensor, or a list of single frames of varying size, as a list of [b, ...] batch tensors."""
     if isinstance(frames, torch.Tensor):
@@ -187,8 +233,9 @@ class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
     def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None,
-                 object_metrics=None):
+                 object_metrics=None, resize=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
+        self.resize = _model_size(resize)
         self.readout = _readout_options(object_depth)
         self.errors = _metric_options(object_metrics)
         self.min_depth, self.max_depth = _depth_range(args)
@@ -218,12 +265,30 @@ class _Ends:
             raise ValueError(f"frames of one batch must crop to one size, got {sorted(sizes)}")
         return sizes.pop()
 
+    def model_size(self, frames: List[torch.Tensor]) -> Tuple[int, int]:
+        """The size the model sees: ``resize``, else the window's."""
+        return self.window_of(frames) if self.resize is None else self.resize
+
+    def taps_of(self, frames: List[torch.Tensor]):
+        """With ``resize``: the device tap tables of the step's window size, uploaded on the current stream when the size is first seen
+        on that device and kept (``hip_ops.frame_resize_taps``); None without."""
+        if self.resize is None:
+            return None
+        Hw, Ww = self.window_of(frames)
+        if not hip_ops.frame_resize_supported(Hw, Ww, *self.resize):
+            raise ValueError(f"resize: a {Hw} x {Ww} window to {self.resize[0]} x {self.resize[1]} shrinks by more than "
+                             f"{hip_ops.FRAME_RESIZE_MAX_RATIO} along an axis (hip_ops.frame_resize_ingest)")
+        return hip_ops.frame_resize_taps(frames[0].device, Hw, Ww, *self.resize)
+
     def ingest(self, frames: List[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``."""
+        """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``.  With ``resize``
+        every frame's window is resized to the model's size by that launch (``hip_ops.frame_resize_ingest``)."""
         for f in frames:
             if f.device.type != "cuda":
                 raise HipLibraryError(f"frames are on {f.device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
-        H, W = self.window_of(frames)
+        Hw, Ww = self.window_of(frames)
+        H, W = self.model_size(frames)
+        taps = self.taps_of(frames)
         B = sum(int(f.shape[0]) for f in frames)
         table = self._on(frames[0].device, False)["table"]
         if out is None:
@@ -233,7 +298,10 @@ class _Ends:
         i = 0
         for f in frames:
             top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            hip_ops.frame_ingest(f, table, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
+            if taps is None:
+                hip_ops.frame_ingest(f, table, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
+            else:
+                hip_ops.frame_resize_ingest(f, table, (H, W), top, left, (Hw, Ww), mirror_too=self.flip_tta, out=out, out_index=i, taps=taps)
             i += int(f.shape[0])
         return out
 
@@ -394,6 +462,13 @@ class Predictor:
     truth is given; ``bin_edges``: those of the un-mirrored forward (a captured graph hands out its static tensor).
     ``model``: GraphBins / AdaBins, or a ``GraphedGraphBins`` captured for the [batch | mirrored batch] shape with
     ``object_group = B`` -- the frames are then ingested straight into its static input and it is called through ``checked``.
+    ``resize``: None (the window must have the model's size, as above), or the model's (H, W): the window -- ``crop``, e.g.
+    ``fit_window(Hs, Ws, H, W)``, else the dataset's rule -- may then have ANY size and is resized to (H, W) by the ingest launch
+    (csrc/frame_resize.hip: antialiased, normalised, mirrored, straight into a captured graph's static input of that shape).  Every
+    output is still written at the WINDOW's size -- the final map is resized to it like to any size -- so ground truth, ``boxes=``,
+    ``intrinsics=`` and the cloud's colour stay in window / source-frame pixels exactly as described here; only boxes fed to the MODEL's
+    object provider live in model-input pixels (``boxes_to_model``).  A window may shrink by at most
+    ``hip_ops.FRAME_RESIZE_MAX_RATIO`` along an axis.
     ``object_depth``: None, or a dict with some of ``quantiles`` / ``shrink`` -- the per-object readout (objcavit_amd/object_depth.py).
     With it, ``boxes=`` of a call -- the boxes a detector found in the B frames, in pixels of the cropped window: a list of [N_i, >= 4]
     tensors / None, an (xywh, counts) pair or a ``PaddedObjects``; independent of the objects the model's provider is fed -- is read out
@@ -417,16 +492,17 @@ class Predictor:
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None,
-                 object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
+                 resize: Optional[Tuple[int, int]] = None, object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None,
+                 object_depth: Optional[dict] = None):
         self.model = model
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
         """(output of the un-mirrored forward, the mirrored forward's output or None): ``validation._forward_pair`` fed by the ingest,
         which writes straight into a captured graph's static input when that has the step's shape."""
         static = getattr(self.model, "static_image", None)
-        fits = static is not None and tuple(static.shape[2:]) == self.ends.window_of(frames)
+        fits = static is not None and tuple(static.shape[2:]) == self.ends.model_size(frames)
         if not self.flip_tta:
             return _call(self.model, self.ends.ingest(frames, out=static if fits and int(static.shape[0]) == B else None)), None
         return _forward_pair(self.model, both=self.ends.ingest(frames, out=static if fits and _joint(self.model, B) else None))
@@ -457,7 +533,9 @@ class PipelinedPredictor(_SlotPipeline):
     set before the HIP runtime starts, like ``PipelinedValidation``.  ``object_depth`` / ``submit(..., boxes=)``: as ``Predictor``'s; the
     readout runs on the slot's stream, a re-run step is read out from the re-run's map.  ``point_cloud`` / ``submit(..., intrinsics=)``:
     likewise; a list of differently sized frames gives one launch pair per frame.  ``object_metrics``: as ``Predictor``'s, on the slot's
-    stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.
+    stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
+    graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
+    have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
 
         pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
         for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
@@ -470,12 +548,12 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
-                 crop: Optional[Tuple[int, int, int, int]] = None, object_metrics: Optional[dict] = None,
-                 point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
+                 crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
+                 object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
@@ -496,7 +574,7 @@ class PipelinedPredictor(_SlotPipeline):
     def _finish(self, out, step: _Step, first_image_id: int) -> PredictResult:
         gt = self.ends.ground_truth(step.depth_gt, self.B)
         out, mirror = _split(out, self.B) if self.flip_tta else (out, None)
-        res = self.ends.finish(out, mirror, self.size, gt, first_image_id, self.want, step.boxes, step.intrinsics)
+        res = self.ends.finish(out, mirror, step.size or self.size, gt, first_image_id, self.want, step.boxes, step.intrinsics)
         return res._replace(bin_edges=res.bin_edges.clone() if (self.want_edges and res.bin_edges is not None) else None)
 
     def collect(self) -> List[PredictResult]:
@@ -512,14 +590,18 @@ class PipelinedPredictor(_SlotPipeline):
         ``object_features``: as ``PipelinedValidation.submit``'s -- a ``Detections`` of the B frames (the model's provider a
         ``DeviceObjectProvider``, with ``mirror_width`` under flip-TTA) is written into the slot's static buffers by one launch."""
         frames = _frame_list(frames_u8, "frames_u8", 4)
-        if sum(int(f.shape[0]) for f in frames) != self.B or self.ends.window_of(frames) != self.size:
+        size = self.ends.window_of(frames)
+        if sum(int(f.shape[0]) for f in frames) != self.B or (size != self.size and self.ends.resize is None):
             raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")
-        held = list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
+        # ``resize``: a window size seen for the first time has its tap tables uploaded HERE, on the caller's stream, which the slot's
+        # stream waits for before its launch; the cache keeps them alive, and they are held like the frames
+        taps = self.ends.taps_of(frames)
+        held = list(taps or ()) + list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
         boxes = self.ends.boxes_on(boxes, frames[0].device, self.B)
         held += list(boxes or ())
         K = self.ends.intrinsics_on(intrinsics, frames[0].device, self.B)
         held += [] if K is None else [K]
-        self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames)), first_image_id,
+        self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames), size), first_image_id,
                      (object_features, object_xywh_list))
         made = self._pending[-1].result
         for t in tuple(getattr(made, "points", None) or ()) + tuple((getattr(made, "object_metrics", None) or ())[:2]):
