@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/objcavit_hip.h"
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -40,6 +42,17 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-x)); }
 __device__ __forceinline__ float fast_silu(float x) { return x * fast_sigmoid(x); }
 
+// the activation codes of the C ABI (OCV_ACT_*, include/objcavit_hip.h): one switch for every epilogue that takes the code at run time
+__device__ __forceinline__ float ocv_act(float v, int act) {
+  switch (act) {
+    case OCV_ACT_RELU: return fmaxf(v, 0.f);
+    case OCV_ACT_LEAKY_RELU: return v > 0.f ? v : 0.01f * v;
+    case OCV_ACT_SILU: return fast_silu(v);
+    case OCV_ACT_SIGMOID: return fast_sigmoid(v);
+    default: return v;
+  }
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // XCD-aware, bijective workgroup map.  The hardware deals workgroup ids round-robin over the eight XCDs (id & 7); this
@@ -56,7 +69,20 @@ __device__ __forceinline__ int ocv_xcd_remap(int wg, int nwg) {
 template <int N>
 __device__ __forceinline__ void ocv_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// Two-term split of an fp32 value into the 2-byte (hi, lo) bit patterns of the "hl32" activation layout (csrc/conv_tile.hpp):
+// "hl32" layout of a split activation: per pixel, per block of 32 channels, 32 hi values followed by their 32 lo values
+// (bf16; hi = bf16(v), lo = bf16(v - hi)); channels padded with zeros to a multiple of 32:
+//   element (pixel m, channel c, part) at  m * 2 Cp + (c >> 5) * 64 + part * 32 + (c & 31)
+// One (pixel, 32-channel) chunk -- what a K step of the implicit GEMM consumes -- is ONE 128-byte line holding both
+// parts.  With hi and lo in two separate NHWC tensors the same chunk was two half lines in two places, whose other
+// halves (the next K chunk) were needed nine taps later, after the 4 MB L2 had lost them: every line came in from
+// beyond L2 twice (FETCH_SIZE 2.2x the algorithmic bytes) and the LDS-DMA pieces touched twice as many lines.
+// ONE expression for both forms: an index (base = 0) and a pointer to the element (the MBConv kernels add the terms to their
+// base pointer one at a time; base + hl_index(...) folds differently and changes their instruction streams).
+template <class T>
+__device__ __forceinline__ T hl_at(T base, long m, int c, int Cp) { return base + m * 2 * Cp + (c >> 5) * 64 + (c & 31); }
+__device__ __forceinline__ long hl_index(long m, int c, int Cp) { return hl_at(0L, m, c, Cp); }
+
+// Two-term split of an fp32 value into the 2-byte (hi, lo) bit patterns of the "hl32" activation layout (hl_index above):
 // F16 = fp16 terms (hi = fp16(v), lo = fp16(v - hi): 22 bits down to an absolute floor of 2^-25, range +-65504 -- beyond it inf,
 // loud), else bf16 terms (16 bits, fp32's range).  Which one a tensor holds is the producing call's ``f16`` flag; consumers are
 // told the same flag.

@@ -4,11 +4,12 @@
 //                      (conv_halo_dma_kernel), the split-K finish pass, their dispatch and ocv_conv_launch
 //   conv_winograd.hip  F(4x4, 3x3): transforms around a batch of 36 GEMMs on the tap ring
 //   patch_embed.hip    the split patch embedding: 16 GEMMs of the tap ring over one K axis
-// Here: the tile sizes, the launch arguments, the (hi, lo) split and the hl32 layout, and the pieces of a 256 x 128 tile's K
+// Here: the tile sizes, the launch arguments, the (hi, lo) split (the hl32 layout itself: hl_index, common.hpp), and the pieces of a 256 x 128 tile's K
 // step and epilogue that the two LDS-DMA kernels have in common -- ONE copy of the MFMA triple, the activation, both
 // store passes and the weight-row DMA, so that the kernels' bit-identical results do not rest on copies kept in step by hand.
 #pragma once
 #include "common.hpp"
+#include "lds_dma.hpp"
 #include "../../include/objcavit_hip.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -115,19 +116,6 @@ __device__ __forceinline__ f32x4 join4_bits(const void* p, int lo_off, bool f16)
   return r;
 }
 
-// "hl32" layout of a split activation: per pixel, per block of 32 channels, 32 hi values followed by their 32 lo values
-// (bf16; hi = bf16(v), lo = bf16(v - hi)); channels padded with zeros to a multiple of 32:
-//   element (pixel m, channel c, part) at  m * 2 Cp + (c >> 5) * 64 + part * 32 + (c & 31)
-// One (pixel, 32-channel) chunk -- what a K step of the implicit GEMM consumes -- is ONE 128-byte line holding both
-// parts.  With hi and lo in two separate NHWC tensors the same chunk was two half lines in two places, whose other
-// halves (the next K chunk) were needed nine taps later, after the 4 MB L2 had lost them: every line came in from
-// beyond L2 twice (FETCH_SIZE 2.2x the algorithmic bytes) and the LDS-DMA pieces touched twice as many lines.
-__device__ __forceinline__ long hl_index(long m, int c, int Cp) { return m * 2 * Cp + (c >> 5) * 64 + (c & 31); }
-
-// zero-initialised: source of padded taps.  ``static``: the library is built without relocatable device code, so a __device__
-// symbol is visible to the kernels of its own file only -- every file that includes this header has its own 256-byte page.
-static __device__ __attribute__((aligned(256))) float ocv_zero_page[64];
-
 __device__ __forceinline__ float conv_act(float v, int act) {
   if (act == OCV_ACT_LEAKY_RELU) return v > 0.f ? v : 0.01f * v;
   if (act == OCV_ACT_SILU) return fast_silu(v);
@@ -138,9 +126,6 @@ __device__ __forceinline__ float conv_act(float v, int act) {
 // ---------------------------------------------------------------------------
 // The LDS-DMA kernels' tile (conv_dma.hip): unpadded 64-byte LDS rows, 16 x 16 x 32 MFMAs, accumulators parked in LDS
 // ---------------------------------------------------------------------------
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int DROW = 64;                                        // bytes per LDS row (32 bf16), unpadded
 constexpr int DA = CBM * DROW, DB = CBN * DROW;                 // 16384, 8192
 constexpr int DBUF = 2 * DA + 2 * DB;                           // 49152 per buffer

@@ -1,5 +1,5 @@
 // Depthwise k x k convolution (+ folded BatchNorm + SiLU) that also produces the squeeze-excite pooling sums, and the
-// squeeze-excite gate computed from them -- 3 launches per MBConv block where csrc/encoder_nhwc.hip needs 5
+// squeeze-excite gate computed from them (csrc/se_gate.hip) -- 3 launches per MBConv block where the plain kernels need 5
 // (depthwise, channel sum, mean, hidden layer, gate), and no second pass over the depthwise output (the largest
 // activations of the network: 295 MB at 120 x 160 x 240 x 16 images).
 // Row N1 of SURVEY.md section 8; the reference runs conv_dw / bn / act / se of the hub backbone's blocks
@@ -14,15 +14,12 @@
 //   brings every input row of the tile into an LDS ring once (LDS-DMA), the consumers read the window from there with
 //   the weights in registers; same arithmetic, bit-identical outputs, part[b][tile][c] with its own tile count.
 //   ocv_depthwise_set_dispatch chooses between the two (tests, tools); automatic: see dw_use_rows.
-// se_hidden_partials_kernel + se_gate_hid_kernel: pooling mean from the partials, hidden layer, gate (see there).
+// The gate from the partials: csrc/se_gate.hip.
 #include <stdlib.h>
 
-#include "common.hpp"
-#include "../../include/objcavit_hip.h"
+#include "mbconv_tile.hpp"
 
 namespace {
-
-typedef __bf16 dw_bf16x4 __attribute__((ext_vector_type(4)));
 
 struct DWSArgs {
   const float *in, *w, *bias;
@@ -52,18 +49,9 @@ __global__ __launch_bounds__(256, 2) void dw_slide_kernel(DWSArgs p) {
   const int tid = threadIdx.x;
   const int q = tid % p.QL, pl = tid / p.QL;
   const int c4n = p.C >> 2;
-  // XCD-aware, bijective workgroup -> (image, chunk, tile) map: consecutive workgroup ids go round-robin to the 8 XCDs,
-  // and neighbouring work items share halo rows / columns through their XCD's own L2.  Give every XCD a contiguous run
-  // of tiles (whole images at bs = 16).
   int tile, chunk;
   long b;
-  {
-    const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
-    tile = wg % p.tiles;
-    const int rest = wg / p.tiles;
-    chunk = rest % p.chunks;
-    b = rest / p.chunks;
-  }
+  dw_xcd_decode(p.tiles, p.chunks, tile, chunk, b);
   const int cq = chunk * p.QL + q;
   const int wi = tile * p.PL + pl;
   const bool active = pl < p.PL && cq < c4n && wi < p.nwork;
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void dw_slide_kernel(DWSArgs p) {
     const float* ib = p.in + b * (long)p.H * p.W * p.C + c;
     const long opix = (b * p.Ho + y0) * (long)p.Wo + ox;
     float* ob = p.out + opix * p.C + c;
-    __bf16* ohb = p.out_hl + opix * 2 * p.C + (c >> 5) * 64 + (c & 31);       // hl32: hi quad here, lo quad 32 elements on
+    __bf16* ohb = hl_at(p.out_hl, opix, c, p.C);                            // hl32: hi quad here, lo quad 32 elements on
     float4 win[K][NIN];
     auto load_row = [&](int rel, float4 (&dst)[NIN]) {
       const int iy = iyb + rel;
@@ -135,9 +123,7 @@ __global__ __launch_bounds__(256, 2) void dw_slide_kernel(DWSArgs p) {
               const float4 w4 = WLDS ? wsh[(r * K + j) * 64 + q] : wv[WLDS ? 0 : r * K + j];
 #pragma unroll
               for (int o = 0; o < PX; ++o) {
-                const float4 x = win[(S * u + r) % K][o * S + j];
-                acc[o].x = fmaf(w4.x, x.x, acc[o].x); acc[o].y = fmaf(w4.y, x.y, acc[o].y);
-                acc[o].z = fmaf(w4.z, x.z, acc[o].z); acc[o].w = fmaf(w4.w, x.w, acc[o].w);
+                acc[o] = fma4(w4, win[(S * u + r) % K][o * S + j], acc[o]);
               }
             }
           }
@@ -149,12 +135,11 @@ __global__ __launch_bounds__(256, 2) void dw_slide_kernel(DWSArgs p) {
 #pragma unroll
           for (int o = 0; o < PX; ++o) {
             if (ox + o < p.Wo) {
-              float4 r4 = acc[o];
-              r4.x = fast_silu(r4.x); r4.y = fast_silu(r4.y); r4.z = fast_silu(r4.z); r4.w = fast_silu(r4.w);
+              const float4 r4 = silu4(acc[o]);
               if (p.out != nullptr) *reinterpret_cast<float4*>(ob + (roff + o) * p.C) = r4;
               if (p.out_hl != nullptr) {
-                const float f[4] = {r4.x, r4.y, r4.z, r4.w};
-                dw_bf16x4 h, l;
+                const float f[4] = {r4.x, r4.y, r4.z, r4.w};     // (split4 written out: through the helper, in every form tried,
+                bf16x4 h, l;                                      //  dw_slide_kernel<5, 2, 1> is compiled to another stream)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                   const __bf16 hb = (__bf16)f[e];
@@ -162,8 +147,8 @@ __global__ __launch_bounds__(256, 2) void dw_slide_kernel(DWSArgs p) {
                   l[e] = (__bf16)(f[e] - (float)hb);
                 }
                 __bf16* d = ohb + (roff + o) * 2 * p.C;
-                *reinterpret_cast<dw_bf16x4*>(d) = h;
-                *reinterpret_cast<dw_bf16x4*>(d + 32) = l;
+                *reinterpret_cast<bf16x4*>(d) = h;
+                *reinterpret_cast<bf16x4*>(d + 32) = l;
               }
               sum.x += r4.x; sum.y += r4.y; sum.z += r4.z; sum.w += r4.w;
             }
@@ -227,11 +212,6 @@ DWSGeom dws_geom(int B, int C, int Ho, int Wo, int k, int stride) {
 // REGISTERS (the window's 100 - 120 registers are free: it stays in LDS), and dw_slide_kernel's arithmetic statement
 // for statement (acc = bias, fmaf over r outer / j inner, padded taps multiplied as zeros, fast_silu): out and out_hl
 // are bit-identical to its.  part[b][tile][c]: one row per workgroup tile.
-__device__ __attribute__((aligned(256))) float ocv_dw_zero_page[64];         // zero-initialised: source of padded pixels
-
-typedef __attribute__((address_space(1))) const void* dwr_gptr;
-typedef __attribute__((address_space(3))) void* dwr_lptr;
-
 struct DWRArgs {
   const float *in, *w, *bias;
   float *out, *part;
@@ -274,13 +254,7 @@ __global__ __launch_bounds__(dwr_threads(S), dwr_waves_per_simd(S)) void dw_rows
   const int c4n = p.C >> 2;
   int tile, chunk;
   long b;
-  {                                                           // XCD-aware, as dw_slide_kernel
-    const int wg = ocv_xcd_remap(blockIdx.x, gridDim.x);
-    tile = wg % p.tiles;
-    const int rest = wg / p.tiles;
-    chunk = rest % p.chunks;
-    b = rest / p.chunks;
-  }
+  dw_xcd_decode(p.tiles, p.chunks, tile, chunk, b);
   const int band = tile / p.nxt, xt = tile - band * p.nxt;
   const int y0 = band * p.TH, y1 = min(p.Ho, y0 + p.TH);      // one barrier per output row, the same for all five wavefronts
   const int iyb = y0 * S - p.pad_t;                           // input row of window row 0
@@ -306,8 +280,8 @@ __global__ __launch_bounds__(dwr_threads(S), dwr_waves_per_simd(S)) void dw_rows
       __attribute__((address_space(3))) float4* dst = (__attribute__((address_space(3))) float4*)ring + slot * ROWE;
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
-        const float* src = rok && coff[j] >= 0 ? row + coff[j] : ocv_dw_zero_page;
-        __builtin_amdgcn_global_load_lds((dwr_gptr)src, (dwr_lptr)(dst + j * 64), 16, 0, 0);
+        const float* src = rok && coff[j] >= 0 ? row + coff[j] : ocv_zero_page;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + j * 64), 16, 0, 0);
       }
     };
 #pragma unroll
@@ -341,7 +315,7 @@ __global__ __launch_bounds__(dwr_threads(S), dwr_waves_per_simd(S)) void dw_rows
     float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
     const long opix = (b * p.Ho + y0) * (long)p.Wo + ox;
     float* ob = p.out + opix * p.C + c;
-    __bf16* ohb = p.out_hl + opix * 2 * p.C + (c >> 5) * 64 + (c & 31);       // hl32: hi quad here, lo quad 32 elements on
+    __bf16* ohb = hl_at(p.out_hl, opix, c, p.C);                            // hl32: hi quad here, lo quad 32 elements on
     const float4* rp = ring + pl * PX * S * QLP + q;
     int s0 = 0;                                               // slot of the window's first row
 #pragma unroll 1
@@ -366,8 +340,7 @@ __global__ __launch_bounds__(dwr_threads(S), dwr_waves_per_simd(S)) void dw_rows
             const float4 w4 = wv[r * K + j];
 #pragma unroll
             for (int o = 0; o < PX; ++o) {
-              acc[o].x = fmaf(w4.x, x[o * S + j].x, acc[o].x); acc[o].y = fmaf(w4.y, x[o * S + j].y, acc[o].y);
-              acc[o].z = fmaf(w4.z, x[o * S + j].z, acc[o].z); acc[o].w = fmaf(w4.w, x[o * S + j].w, acc[o].w);
+              acc[o] = fma4(w4, x[o * S + j], acc[o]);
             }
           }
         }
@@ -378,26 +351,18 @@ __global__ __launch_bounds__(dwr_threads(S), dwr_waves_per_simd(S)) void dw_rows
           // and adds zero: no branch, so the compiler cannot sink that column's FMAs into one.
           const bool ok = o == 0 || ok1;
           const int oo = ok ? o : 0;
-          float4 r4 = acc[o];
-          r4.x = fast_silu(r4.x); r4.y = fast_silu(r4.y); r4.z = fast_silu(r4.z); r4.w = fast_silu(r4.w);
+          float4 r4 = silu4(acc[o]);
           if (o > 0) {
-            float4 f4 = acc[0];
-            f4.x = fast_silu(f4.x); f4.y = fast_silu(f4.y); f4.z = fast_silu(f4.z); f4.w = fast_silu(f4.w);
+            const float4 f4 = silu4(acc[0]);
             r4.x = ok ? r4.x : f4.x; r4.y = ok ? r4.y : f4.y; r4.z = ok ? r4.z : f4.z; r4.w = ok ? r4.w : f4.w;
           }
           if (p.out != nullptr) *reinterpret_cast<float4*>(ob + (roff + oo) * p.C) = r4;
           if (p.out_hl != nullptr) {
-            const float f[4] = {r4.x, r4.y, r4.z, r4.w};
-            dw_bf16x4 h, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const __bf16 hb = (__bf16)f[e];
-              h[e] = hb;
-              l[e] = (__bf16)(f[e] - (float)hb);
-            }
+            bf16x4 h, l;
+            split4(r4, h, l);
             __bf16* d = ohb + (roff + oo) * 2 * p.C;
-            *reinterpret_cast<dw_bf16x4*>(d) = h;
-            *reinterpret_cast<dw_bf16x4*>(d + 32) = l;
+            *reinterpret_cast<bf16x4*>(d) = h;
+            *reinterpret_cast<bf16x4*>(d + 32) = l;
           }
           sum.x += ok ? r4.x : 0.f; sum.y += ok ? r4.y : 0.f; sum.z += ok ? r4.z : 0.f; sum.w += ok ? r4.w : 0.f;
         }
@@ -461,296 +426,6 @@ bool dw_use_rows(int C, int Ho, int Wo, int k, int stride) {
   return mode == 2 || stride == 1 || (long)Ho * Wo >= 1200;
 }
 
-// squeeze-excite gate from the pooling partials, two small launches (both latency-bound, so both are spread wide):
-//   se_hidden_partials_kernel  grid (ceil(R / 16), B): mean[c] = (sum_tile part) / P into LDS (every workgroup of an
-//                              image repeats this: tiles x C floats from L2), then one wavefront per hidden unit:
-//                              hid[b][r] = silu(b1[r] + W1[r] . mean)
-//   se_gate_hid_kernel         grid (ceil(C / 256), B): gate[b][c] = sigmoid(b2[c] + sum_r W2t[r][c] hid[b][r])
-__global__ __launch_bounds__(1024) void se_hidden_partials_kernel(const float* __restrict__ part, int tiles, float inv,
-                                                                 const float* __restrict__ w1, const float* __restrict__ b1,
-                                                                 float* __restrict__ hid, int C, int R) {
-  extern __shared__ float sm[];            // mean[C] | red[TG][C]
-  float* mean = sm;
-  float* red = sm + C;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long b = blockIdx.y;
-  const float* pb = part + b * tiles * (long)C;
-  // pooling: item = (channel QUAD, row group); every thread keeps eight independent 16-byte loads in flight.  (Round 4: the first
-  // version summed one float per load, four in flight -- at bs 1, where a depthwise launch leaves up to 600 partial rows per
-  // image, that was 38 dependent round trips and 10.7 us per launch, 0.42 ms of a 4 ms forward; profiles/r04a_*.)  Out-of-range
-  // rows are clamped to a valid address and selected away: no branch around a load.  Fixed order: rows ascending within a group,
-  // groups ascending.
-  const int nq = C >> 2;                    // C % 4 == 0 (the depthwise kernels' contract)
-  const int TG = nq >= 1024 ? 1 : min(tiles, 1024 / nq);
-  for (int idx = tid; idx < TG * nq; idx += 1024) {
-    const int q = idx % nq, tg = idx / nq;
-    float4 a[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* src = pb + 4 * q;
-    for (int t0 = tg; t0 < tiles; t0 += 8 * TG) {
-      float4 u[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) u[j] = ld4(src + (long)min(t0 + j * TG, tiles - 1) * C);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const bool ok = t0 + j * TG < tiles;
-        a[j].x += ok ? u[j].x : 0.f; a[j].y += ok ? u[j].y : 0.f; a[j].z += ok ? u[j].z : 0.f; a[j].w += ok ? u[j].w : 0.f;
-      }
-    }
-    float4 r;
-    r.x = ((a[0].x + a[1].x) + (a[2].x + a[3].x)) + ((a[4].x + a[5].x) + (a[6].x + a[7].x));
-    r.y = ((a[0].y + a[1].y) + (a[2].y + a[3].y)) + ((a[4].y + a[5].y) + (a[6].y + a[7].y));
-    r.z = ((a[0].z + a[1].z) + (a[2].z + a[3].z)) + ((a[4].z + a[5].z) + (a[6].z + a[7].z));
-    r.w = ((a[0].w + a[1].w) + (a[2].w + a[3].w)) + ((a[4].w + a[5].w) + (a[6].w + a[7].w));
-    *reinterpret_cast<float4*>(red + tg * C + 4 * q) = r;
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += 1024) {
-    float s = red[c];
-    for (int tg = 1; tg < TG; ++tg) s += red[tg * C + c];
-    mean[c] = s * inv;
-  }
-  __syncthreads();
-  const int r = blockIdx.x * 16 + wave;
-  if (r >= R) return;
-  // one wavefront per hidden unit: a lane takes channel QUADS lane, lane + 64, ... -- 16-byte loads, four of them in flight
-  // (C <= 1024: the whole row of W1 in one round trip; one float per load took C / 256 dependent rounds)
-  const float* wr = w1 + (long)r * C;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int q = lane;
-  for (; q + 192 < nq; q += 256) {
-    const float4 u0 = ld4(wr + 4 * q), u1 = ld4(wr + 4 * (q + 64)), u2 = ld4(wr + 4 * (q + 128)), u3 = ld4(wr + 4 * (q + 192));
-    const float4 m0 = *reinterpret_cast<const float4*>(mean + 4 * q), m1 = *reinterpret_cast<const float4*>(mean + 4 * (q + 64));
-    const float4 m2 = *reinterpret_cast<const float4*>(mean + 4 * (q + 128)), m3 = *reinterpret_cast<const float4*>(mean + 4 * (q + 192));
-    s0 = fmaf(u0.x, m0.x, fmaf(u0.y, m0.y, fmaf(u0.z, m0.z, fmaf(u0.w, m0.w, s0))));
-    s1 = fmaf(u1.x, m1.x, fmaf(u1.y, m1.y, fmaf(u1.z, m1.z, fmaf(u1.w, m1.w, s1))));
-    s2 = fmaf(u2.x, m2.x, fmaf(u2.y, m2.y, fmaf(u2.z, m2.z, fmaf(u2.w, m2.w, s2))));
-    s3 = fmaf(u3.x, m3.x, fmaf(u3.y, m3.y, fmaf(u3.z, m3.z, fmaf(u3.w, m3.w, s3))));
-  }
-  for (; q < nq; q += 64) {
-    const float4 u0 = ld4(wr + 4 * q);
-    const float4 m0 = *reinterpret_cast<const float4*>(mean + 4 * q);
-    s0 = fmaf(u0.x, m0.x, fmaf(u0.y, m0.y, fmaf(u0.z, m0.z, fmaf(u0.w, m0.w, s0))));
-  }
-  const float s = wave_sum((s0 + s1) + (s2 + s3));
-  if (lane == 0) hid[b * R + r] = fast_silu(s + b1[r]);
-}
-
-__global__ __launch_bounds__(256) void se_gate_hid_kernel(const float* __restrict__ hid, const float* __restrict__ w2t,
-                                                          const float* __restrict__ b2, float* __restrict__ gate, int C,
-                                                          int R) {
-  __shared__ float hs[256];
-  const long b = blockIdx.y;
-  if (threadIdx.x < R) hs[threadIdx.x] = hid[b * R + threadIdx.x];
-  __syncthreads();
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  const float* w = w2t + c;
-  float s0 = b2[c], s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int r = 0;
-  for (; r + 15 < R; r += 16) {                       // sixteen loads in flight (four were: R / 4 dependent round trips)
-    float u[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) u[j] = w[(long)(r + j) * C];
-#pragma unroll
-    for (int j = 0; j < 16; j += 4) {
-      s0 = fmaf(u[j], hs[r + j], s0);
-      s1 = fmaf(u[j + 1], hs[r + j + 1], s1);
-      s2 = fmaf(u[j + 2], hs[r + j + 2], s2);
-      s3 = fmaf(u[j + 3], hs[r + j + 3], s3);
-    }
-  }
-  for (; r + 3 < R; r += 4) {
-    s0 = fmaf(w[(long)r * C], hs[r], s0);
-    s1 = fmaf(w[(long)(r + 1) * C], hs[r + 1], s1);
-    s2 = fmaf(w[(long)(r + 2) * C], hs[r + 2], s2);
-    s3 = fmaf(w[(long)(r + 3) * C], hs[r + 3], s3);
-  }
-  for (; r < R; ++r) s0 = fmaf(w[(long)r * C], hs[r], s0);
-  gate[b * C + c] = fast_sigmoid((s0 + s1) + (s2 + s3));
-}
-
-// Both launches above as ONE, for the blocks whose squeeze-excite weights are small (round 4: B5's stages 1 - 5, 27 of 39 blocks):
-// grid (ceil(C / 256), B), 1024 threads; every workgroup of an image repeats the pooling and ALL hidden units (<= 64 of them: W1 is
-// <= 186 KB, L2-resident) and then forms the gate of its own 256 channels.  The arithmetic is the two kernels' own, statement for
-// statement (same thread -> element maps, same summation orders), so the gate is bit-identical to theirs; what goes away is one
-// launch floor (~4.5 us) and the hidden units' round trip through memory: 7.3 + 5.1 -> ~8.5 us at bs 1.
-__global__ __launch_bounds__(1024) void se_fused_small_kernel(const float* __restrict__ part, int tiles, float inv,
-                                                             const float* __restrict__ w1, const float* __restrict__ b1,
-                                                             const float* __restrict__ w2t, const float* __restrict__ b2,
-                                                             float* __restrict__ gate, int C, int R) {
-  extern __shared__ float sm[];            // mean[C] | red[TG][C] | hs[128]
-  float* mean = sm;
-  float* red = sm + C;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long b = blockIdx.y;
-  const float* pb = part + b * tiles * (long)C;
-  const int nq = C >> 2;
-  const int TG = nq >= 1024 ? 1 : min(tiles, 1024 / nq);
-  float* hs = red + (size_t)TG * C;
-  for (int idx = tid; idx < TG * nq; idx += 1024) {
-    const int q = idx % nq, tg = idx / nq;
-    float4 a[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float* src = pb + 4 * q;
-    for (int t0 = tg; t0 < tiles; t0 += 8 * TG) {
-      float4 u[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) u[j] = ld4(src + (long)min(t0 + j * TG, tiles - 1) * C);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const bool ok = t0 + j * TG < tiles;
-        a[j].x += ok ? u[j].x : 0.f; a[j].y += ok ? u[j].y : 0.f; a[j].z += ok ? u[j].z : 0.f; a[j].w += ok ? u[j].w : 0.f;
-      }
-    }
-    float4 r;
-    r.x = ((a[0].x + a[1].x) + (a[2].x + a[3].x)) + ((a[4].x + a[5].x) + (a[6].x + a[7].x));
-    r.y = ((a[0].y + a[1].y) + (a[2].y + a[3].y)) + ((a[4].y + a[5].y) + (a[6].y + a[7].y));
-    r.z = ((a[0].z + a[1].z) + (a[2].z + a[3].z)) + ((a[4].z + a[5].z) + (a[6].z + a[7].z));
-    r.w = ((a[0].w + a[1].w) + (a[2].w + a[3].w)) + ((a[4].w + a[5].w) + (a[6].w + a[7].w));
-    *reinterpret_cast<float4*>(red + tg * C + 4 * q) = r;
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += 1024) {
-    float s = red[c];
-    for (int tg = 1; tg < TG; ++tg) s += red[tg * C + c];
-    mean[c] = s * inv;
-  }
-  __syncthreads();
-  for (int r = wave; r < R; r += 16) {                 // every hidden unit, one wavefront each (se_hidden_partials_kernel's dot)
-    const float* wr = w1 + (long)r * C;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int q = lane;
-    for (; q + 192 < nq; q += 256) {
-      const float4 u0 = ld4(wr + 4 * q), u1 = ld4(wr + 4 * (q + 64)), u2 = ld4(wr + 4 * (q + 128)), u3 = ld4(wr + 4 * (q + 192));
-      const float4 m0 = *reinterpret_cast<const float4*>(mean + 4 * q), m1 = *reinterpret_cast<const float4*>(mean + 4 * (q + 64));
-      const float4 m2 = *reinterpret_cast<const float4*>(mean + 4 * (q + 128)), m3 = *reinterpret_cast<const float4*>(mean + 4 * (q + 192));
-      s0 = fmaf(u0.x, m0.x, fmaf(u0.y, m0.y, fmaf(u0.z, m0.z, fmaf(u0.w, m0.w, s0))));
-      s1 = fmaf(u1.x, m1.x, fmaf(u1.y, m1.y, fmaf(u1.z, m1.z, fmaf(u1.w, m1.w, s1))));
-      s2 = fmaf(u2.x, m2.x, fmaf(u2.y, m2.y, fmaf(u2.z, m2.z, fmaf(u2.w, m2.w, s2))));
-      s3 = fmaf(u3.x, m3.x, fmaf(u3.y, m3.y, fmaf(u3.z, m3.z, fmaf(u3.w, m3.w, s3))));
-    }
-    for (; q < nq; q += 64) {
-      const float4 u0 = ld4(wr + 4 * q);
-      const float4 m0 = *reinterpret_cast<const float4*>(mean + 4 * q);
-      s0 = fmaf(u0.x, m0.x, fmaf(u0.y, m0.y, fmaf(u0.z, m0.z, fmaf(u0.w, m0.w, s0))));
-    }
-    const float s = wave_sum((s0 + s1) + (s2 + s3));
-    if (lane == 0) hs[r] = fast_silu(s + b1[r]);
-  }
-  __syncthreads();
-  const int c = blockIdx.x * 256 + tid;
-  if (tid >= 256 || c >= C) return;
-  const float* w = w2t + c;
-  float s0 = b2[c], s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int r = 0;
-  for (; r + 15 < R; r += 16) {
-    float u[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) u[j] = w[(long)(r + j) * C];
-#pragma unroll
-    for (int j = 0; j < 16; j += 4) {
-      s0 = fmaf(u[j], hs[r + j], s0);
-      s1 = fmaf(u[j + 1], hs[r + j + 1], s1);
-      s2 = fmaf(u[j + 2], hs[r + j + 2], s2);
-      s3 = fmaf(u[j + 3], hs[r + j + 3], s3);
-    }
-  }
-  for (; r + 3 < R; r += 4) {
-    s0 = fmaf(w[(long)r * C], hs[r], s0);
-    s1 = fmaf(w[(long)(r + 1) * C], hs[r + 1], s1);
-    s2 = fmaf(w[(long)(r + 2) * C], hs[r + 2], s2);
-    s3 = fmaf(w[(long)(r + 3) * C], hs[r + 3], s3);
-  }
-  for (; r < R; ++r) s0 = fmaf(w[(long)r * C], hs[r], s0);
-  gate[b * C + c] = fast_sigmoid((s0 + s1) + (s2 + s3));
-}
-
-// The gate FOLDED INTO THE PROJECT WEIGHTS, per image: Wg[b][n][k] = W[n][k] * gate[b][k], split (hi = bf16, lo = bf16 of the
-// rest) and packed in the B-operand order of the pointwise kernels ([jt][s][part][lane][8], hip_ops.SplitWeight) -- so that
-// the project convolution's row operand is the depthwise output AS STORED (hl32, LDS-DMA) instead of rows re-gated and
-// re-split by every workgroup that touches them.  Grid (ceil(K / 64), B): a workgroup forms the gate of its 64 input
-// channels (same summation order as se_gate_hid_kernel) and scales / splits / packs their column block of W for all N
-// rows; thread = (octet of 8 inputs, one of 32 consecutive output rows): a wavefront half writes 512 contiguous bytes.
-__global__ __launch_bounds__(256) void se_gate_weights_kernel(const float* __restrict__ hid, const float* __restrict__ w2t,
-                                                              const float* __restrict__ b2, const float* __restrict__ W,
-                                                              __bf16* __restrict__ wpk, long img_elems, float* __restrict__ gate,
-                                                              int C, int R, int N) {
-  __shared__ float hs[256];
-  __shared__ float gs[64];
-  const long b = blockIdx.y;
-  const int tid = threadIdx.x;
-  const int k0 = blockIdx.x * 64;
-  if (tid < R) hs[tid] = hid[b * R + tid];
-  __syncthreads();
-  if (tid < 64) {
-    const int c = k0 + tid;
-    float g = 0.f;                                   // inputs past C (K padded to 16): weight columns of zeros
-    if (c < C) {
-      const float* w = w2t + c;
-      float s0 = b2[c], s1 = 0.f, s2 = 0.f, s3 = 0.f;
-      int r = 0;
-      for (; r + 15 < R; r += 16) {                   // sixteen loads in flight, the summation order of se_gate_hid_kernel
-        float u[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) u[j] = w[(long)(r + j) * C];
-#pragma unroll
-        for (int j = 0; j < 16; j += 4) {
-          s0 = fmaf(u[j], hs[r + j], s0);
-          s1 = fmaf(u[j + 1], hs[r + j + 1], s1);
-          s2 = fmaf(u[j + 2], hs[r + j + 2], s2);
-          s3 = fmaf(u[j + 3], hs[r + j + 3], s3);
-        }
-      }
-      for (; r + 3 < R; r += 4) {
-        s0 = fmaf(w[(long)r * C], hs[r], s0);
-        s1 = fmaf(w[(long)(r + 1) * C], hs[r + 1], s1);
-        s2 = fmaf(w[(long)(r + 2) * C], hs[r + 2], s2);
-        s3 = fmaf(w[(long)(r + 3) * C], hs[r + 3], s3);
-      }
-      for (; r < R; ++r) s0 = fmaf(w[(long)r * C], hs[r], s0);
-      g = fast_sigmoid((s0 + s1) + (s2 + s3));
-      if (gate != nullptr) gate[b * C + c] = g;
-    }
-    gs[tid] = g;
-  }
-  __syncthreads();
-  const int o = tid >> 5, nl = tid & 31;             // octet of the 64-channel block, row inside a 32-row channel tile
-  const int k = k0 + 8 * o;
-  const int Kp = (C + 15) & ~15;
-  if (k >= Kp) return;
-  const int nsteps = Kp >> 4, s = k >> 4, hh = (k >> 3) & 1;
-  float g8[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) g8[e] = gs[8 * o + e];
-  __bf16* ob = wpk + b * img_elems;
-  const int ntl = (N + 31) >> 5;
-  for (int jt = 0; jt < ntl; ++jt) {
-    const int n = jt * 32 + nl;
-    float f[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = 0.f;
-    if (n < N && k < C) {                            // C is a multiple of 8: an octet is inside or outside as a whole
-      const float4 u = ld4(W + (long)n * C + k), v = ld4(W + (long)n * C + k + 4);
-      f[0] = u.x * g8[0]; f[1] = u.y * g8[1]; f[2] = u.z * g8[2]; f[3] = u.w * g8[3];
-      f[4] = v.x * g8[4]; f[5] = v.y * g8[5]; f[6] = v.z * g8[6]; f[7] = v.w * g8[7];
-    }
-    typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-    bf16x8_t h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const __bf16 hb = (__bf16)f[e];
-      h[e] = hb;
-      l[e] = (__bf16)(f[e] - (float)hb);
-    }
-    __bf16* d = ob + (((long)jt * nsteps + s) * 2) * 512 + (hh * 32 + nl) * 8;
-    *reinterpret_cast<bf16x8_t*>(d) = h;
-    *reinterpret_cast<bf16x8_t*>(d + 512) = l;
-  }
-}
-
 template <int K, int S, int PX>
 int launch_dws(const DWSArgs& a, const DWSGeom& g, int B, hipStream_t st) {
   hipLaunchKernelGGL((dw_slide_kernel<K, S, PX>), dim3((unsigned)((long)g.tiles * g.chunks * B)), dim3(256), 0, st, a);
@@ -760,11 +435,7 @@ int launch_dws(const DWSArgs& a, const DWSGeom& g, int B, hipStream_t st) {
 
 template <int S, int QLP>
 int launch_dwr(const DWRArgs& a, int B, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dw_rows_kernel<S, QLP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  ocv_allow_dynamic_lds<dw_rows_kernel<S, QLP>>();
   constexpr size_t lds = DWRShape<S, QLP>::LDS;
   hipLaunchKernelGGL((dw_rows_kernel<S, QLP>), dim3((unsigned)((long)a.tiles * a.chunks * B)), dim3(dwr_threads(S)), lds, st, a);
   OCV_CHECK_LAUNCH("ocv_depthwise_conv_nhwc_sum_fwd(rows)");
@@ -791,16 +462,14 @@ extern "C" int ocv_depthwise_conv_nhwc_sum_fwd(const float* in, const float* w, 
   return ocv_depthwise_conv_nhwc_sum_hl_fwd(in, w, bias, out, nullptr, part, B, C, H, W, k, stride, pad_t, pad_l, Ho, Wo, stream);
 }
 
-namespace {
-int dws_run(const float* in, const float* w, const float* bias, float* out, void* out_hl, float* part,
-            int B, int C, int H, int W, int k, int stride, int pad_t, int pad_l, int Ho, int Wo, ocv_stream_t stream) {
+extern "C" int ocv_depthwise_conv_nhwc_sum_hl_fwd(const float* in, const float* w, const float* bias, float* out, void* out_hl,
+                                                  float* part, int B, int C, int H, int W, int k, int stride, int pad_t,
+                                                  int pad_l, int Ho, int Wo, ocv_stream_t stream) {
   OCV_CHECK_ARG(in && w && (out || out_hl) && part, "ocv_depthwise_conv_nhwc_sum_fwd: null pointer");
   OCV_CHECK_ARG(out_hl == nullptr || (C % 32 == 0 && ocv_aligned16(out_hl)), "ocv_depthwise_conv_nhwc_sum_hl_fwd: the split output needs C to be a multiple of 32 (got %d) and 16-byte alignment", C);
-  OCV_CHECK_ARG(B >= 1 && C >= 4 && C % 4 == 0 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "ocv_depthwise_conv_nhwc_sum_fwd: bad sizes (C must be a multiple of 4)");
-  OCV_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "ocv_depthwise_conv_nhwc_sum_fwd: k must be 3 or 5 and stride 1 or 2");
-  OCV_CHECK_ARG(pad_t >= 0 && pad_l >= 0 && pad_t < k && pad_l < k, "ocv_depthwise_conv_nhwc_sum_fwd: bad padding");
-  OCV_CHECK_ARG((Ho - 1) * stride - pad_t < H && (Wo - 1) * stride - pad_l < W, "ocv_depthwise_conv_nhwc_sum_fwd: output larger than the padded input allows");
-  OCV_CHECK_ARG(ocv_aligned16(in) && ocv_aligned16(w) && ocv_aligned16(out) && ocv_aligned16(bias) && ocv_aligned16(part), "ocv_depthwise_conv_nhwc_sum_fwd: operands must be 16-byte aligned");
+  if (ocv_check_dw_geometry("ocv_depthwise_conv_nhwc_sum_fwd", true, B, C, H, W, k, stride, pad_t, pad_l, Ho, Wo,
+                            ocv_aligned16(in) && ocv_aligned16(w) && ocv_aligned16(out) && ocv_aligned16(bias) && ocv_aligned16(part)) != 0)
+    return -1;
   hipStream_t st = (hipStream_t)stream;
   if (dw_use_rows(C, Ho, Wo, k, stride)) {
     const DWRGeom r = dwr_geom(B, C, Ho, Wo, stride);
@@ -817,57 +486,4 @@ int dws_run(const float* in, const float* w, const float* bias, float* out, void
   if (k == 3 && stride == 2) return launch_dws<3, 2, 2>(a, g, B, st);
   if (k == 5 && stride == 1) return launch_dws<5, 1, 2>(a, g, B, st);
   return launch_dws<5, 2, 1>(a, g, B, st);
-}
-}  // namespace
-
-extern "C" int ocv_depthwise_conv_nhwc_sum_hl_fwd(const float* in, const float* w, const float* bias, float* out, void* out_hl,
-                                                  float* part, int B, int C, int H, int W, int k, int stride, int pad_t,
-                                                  int pad_l, int Ho, int Wo, ocv_stream_t stream) {
-  return dws_run(in, w, bias, out, out_hl, part, B, C, H, W, k, stride, pad_t, pad_l, Ho, Wo, stream);
-}
-
-extern "C" int ocv_se_gate_partials_fwd(const float* part, int tiles, long pixels_per_image, const float* w1,
-                                        const float* b1, const float* w2t, const float* b2, float* gate, float* hidden_ws,
-                                        int B, int C, int R, ocv_stream_t stream) {
-  OCV_CHECK_ARG(part && w1 && b1 && w2t && b2 && gate && hidden_ws, "ocv_se_gate_partials_fwd: null pointer");
-  OCV_CHECK_ARG(B >= 1 && B <= 65535 && C >= 1 && R >= 1 && R <= 256 && tiles >= 1 && pixels_per_image >= 1, "ocv_se_gate_partials_fwd: bad sizes (R <= 256)");
-  OCV_CHECK_ARG(C <= 8192 && C % 4 == 0, "ocv_se_gate_partials_fwd: C must be a multiple of 4, at most 8192 (got %d)", C);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)(C + (C >= 4096 ? C : 4096)) * sizeof(float);      // mean[C] | red[TG][C], TG * C <= 4096
-  // (A/B, round 4: limits of 1824 / 76 and 3072 / 128 instead of the two below take stages 6 and 7 in -- measured SLOWER there, every workgroup of an
-  //  image re-reading 0.55 / 1.5 MB of W1: bs 16 1000 -> 996 -> 994 img/s one at a time, bs 1 293 -> 286 -> 284)
-  constexpr int max_c = 1536, max_r = 64;
-  if (C <= max_c && R <= max_r && R <= 128) {                       // small squeeze-excite weights: ONE launch
-    hipLaunchKernelGGL(se_fused_small_kernel, dim3((C + 255) / 256, B), dim3(1024), lds + 128 * sizeof(float), st, part, tiles,
-                       1.0f / (float)pixels_per_image, w1, b1, w2t, b2, gate, C, R);
-    OCV_CHECK_LAUNCH("ocv_se_gate_partials_fwd(fused)");
-    return 0;
-  }
-  hipLaunchKernelGGL(se_hidden_partials_kernel, dim3((R + 15) / 16, B), dim3(1024), lds, st, part, tiles,
-                     1.0f / (float)pixels_per_image, w1, b1, hidden_ws, C, R);
-  OCV_CHECK_LAUNCH("ocv_se_gate_partials_fwd(hidden)");
-  hipLaunchKernelGGL(se_gate_hid_kernel, dim3((C + 255) / 256, B), dim3(256), 0, st, (const float*)hidden_ws, w2t, b2, gate, C, R);
-  OCV_CHECK_LAUNCH("ocv_se_gate_partials_fwd(gate)");
-  return 0;
-}
-
-extern "C" int ocv_se_gate_weights_fwd(const float* part, int tiles, long pixels_per_image, const float* w1, const float* b1,
-                                       const float* w2t, const float* b2, const float* W, void* w_packed, long w_image_elems,
-                                       float* gate, float* hidden_ws, int B, int C, int R, int N, ocv_stream_t stream) {
-  OCV_CHECK_ARG(part && w1 && b1 && w2t && b2 && W && w_packed && hidden_ws, "ocv_se_gate_weights_fwd: null pointer");
-  OCV_CHECK_ARG(B >= 1 && B <= 65535 && C >= 8 && C % 8 == 0 && R >= 1 && R <= 256 && N >= 1 && tiles >= 1 && pixels_per_image >= 1,
-                "ocv_se_gate_weights_fwd: bad sizes (C a multiple of 8, R <= 256)");
-  OCV_CHECK_ARG(C <= 8192, "ocv_se_gate_weights_fwd: C too large (%d)", C);
-  OCV_CHECK_ARG(w_image_elems >= (long)ocv_pointwise_packed_weight_elems(C, N) && (w_image_elems & 7) == 0 && ocv_aligned16(w_packed) && ocv_aligned16(W),
-                "ocv_se_gate_weights_fwd: w_image_elems must hold one packed matrix (ocv_pointwise_packed_weight_elems) and keep 16-byte alignment");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)(C + (C >= 4096 ? C : 4096)) * sizeof(float);      // mean[C] | red[TG][C], TG * C <= 4096
-  hipLaunchKernelGGL(se_hidden_partials_kernel, dim3((R + 15) / 16, B), dim3(1024), lds, st, part, tiles,
-                     1.0f / (float)pixels_per_image, w1, b1, hidden_ws, C, R);
-  OCV_CHECK_LAUNCH("ocv_se_gate_weights_fwd(hidden)");
-  const int Kp = (C + 15) / 16 * 16;
-  hipLaunchKernelGGL(se_gate_weights_kernel, dim3((Kp + 63) / 64, B), dim3(256), 0, st, (const float*)hidden_ws, w2t, b2, W,
-                     (__bf16*)w_packed, w_image_elems, gate, C, R, N);
-  OCV_CHECK_LAUNCH("ocv_se_gate_weights_fwd(gate + weights)");
-  return 0;
 }

@@ -24,16 +24,13 @@
 // LDS slots (otherwise every read would be a 2-way bank conflict).
 // Halo recompute of the GEMM: 340 / 256 pixels (k = 3), 432 / 256 (k = 5) -- the GEMM is a few percent of the block's
 // time at Cin <= 64, which is what this kernel is limited to (A fragments of a pixel tile fully in VGPRs).
-#include "common.hpp"
-#include "../../include/objcavit_hip.h"
+#include "mbconv_tile.hpp"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct FXArgs {
   const float *x, *be, *wd, *bd;
-  const __bf16* wp;                 // packed expand weights (csrc/pointwise_split.hip, w_frag)
+  const __bf16* wp;                 // packed expand weights (w_frag, mbconv_tile.hpp)
   float *y, *part;
   int Cin, mid, H, W, Ho, Wo, pad_t, pad_l;
   int tiles_x, tiles_per_image, nchunks;
@@ -54,21 +51,6 @@ struct FXGeom {
     return S == 1 ? py * IW + px : py * IW + (px >> 1) + (px & 1) * HALF;
   }
 };
-
-__device__ __forceinline__ void fx_split8(const float4 u, const float4 v, bf16x8& hi, bf16x8& lo) {
-  const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)f[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(f[i] - (float)h);
-  }
-}
-
-__device__ __forceinline__ float4 fx_fma4(const float4 w, const float4 v, float4 a) {
-  a.x = fmaf(w.x, v.x, a.x); a.y = fmaf(w.y, v.y, a.y); a.z = fmaf(w.z, v.z, a.z); a.w = fmaf(w.w, v.w, a.w);
-  return a;
-}
 
 template <int K, int S, int KS>
 __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_expand_dw_kernel(FXArgs p) {
@@ -97,9 +79,9 @@ __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_exp
   bf16x8 bh[KS], bl[KS];
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
-    const __bf16* f = p.wp + (((long)chunk * KS + s) * 2) * 512 + lane * 8;
-    bh[s] = *reinterpret_cast<const bf16x8*>(f);
-    bl[s] = *reinterpret_cast<const bf16x8*>(f + 512);
+    const __bf16* f = w_frag(p.wp, chunk, 16 * KS, s, lane);
+    bh[s] = ldb8(f);
+    bl[s] = ldb8(f + 512);
   }
   const bool nok = n0 + l31 < p.mid;
   const float bev = (nok && p.be != nullptr) ? p.be[n0 + l31] : 0.f;
@@ -145,10 +127,8 @@ __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_exp
         const int mt = wave + 4 * (g0 + i);
         if (g0 + i < NMT && mt < G::MT) {
           bf16x8 ah, al;
-          fx_split8(raw[i][s][0], raw[i][s][1], ah, al);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s], acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s], acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s], acc[i], 0, 0, 0);
+          split8(raw[i][s][0], raw[i][s][1], ah, al);
+          acc[i] = mfma3(ah, al, bh[s], bl[s], acc[i]);
         }
       }
 #pragma unroll
@@ -194,7 +174,7 @@ __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_exp
       const int d = li - ky;
       if (d >= 0 && d % S == 0 && d / S < G::NR) {
 #pragma unroll
-        for (int kx = 0; kx < K; ++kx) acc[d / S] = fx_fma4(wdw[ky * K + kx], v[kx], acc[d / S]);
+        for (int kx = 0; kx < K; ++kx) acc[d / S] = fma4(wdw[ky * K + kx], v[kx], acc[d / S]);
       }
     }
   }
@@ -206,8 +186,7 @@ __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_exp
   for (int o = 0; o < G::NR; ++o, orow += ostep) {
     const int oy = oy0 + rg * G::NR + o;
     if (cok && oy < p.Ho && ox < p.Wo) {
-      float4 r = acc[o];
-      r.x = fast_silu(r.x); r.y = fast_silu(r.y); r.z = fast_silu(r.z); r.w = fast_silu(r.w);
+      const float4 r = silu4(acc[o]);
       *reinterpret_cast<float4*>(orow) = r;
       psum.x += r.x; psum.y += r.y; psum.z += r.z; psum.w += r.w;
     }
@@ -227,11 +206,7 @@ __global__ __launch_bounds__(256, K == 3 ? (S == 2 ? 2 : 3) : 1) void mbconv_exp
 template <int K, int S, int KS>
 int fx_launch(const FXArgs& a, int B, hipStream_t st) {
   using G = FXGeom<K, S>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)mbconv_expand_dw_kernel<K, S, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    attr = true;
-  }
+  ocv_allow_dynamic_lds<mbconv_expand_dw_kernel<K, S, KS>>(G::LDS_BYTES);
   const long grid = (long)B * a.tiles_per_image * a.nchunks;
   hipLaunchKernelGGL((mbconv_expand_dw_kernel<K, S, KS>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, st, a);
   OCV_CHECK_LAUNCH("ocv_mbconv_expand_dw_fwd");
@@ -253,19 +228,15 @@ extern "C" int ocv_mbconv_expand_dw_tiles(int Ho, int Wo, int k, int stride) {
   return ((Ho + 7) / 8) * ((Wo + tw - 1) / tw);
 }
 
-namespace {
-int fx_run(const float* x, const void* w_packed, const float* bias_expand, const float* w_dw, const float* bias_dw, float* y,
-           float* part, int B, int H, int W, int Cin, int mid, int k, int stride, int pad_t, int pad_l,
-           int Ho, int Wo, ocv_stream_t stream) {
+extern "C" int ocv_mbconv_expand_dw_fwd(const float* x, const void* w_packed, const float* bias_expand, const float* w_dw,
+                                        const float* bias_dw, float* y, float* part, int B, int H, int W, int Cin, int mid,
+                                        int k, int stride, int pad_t, int pad_l, int Ho, int Wo, ocv_stream_t stream) {
   OCV_CHECK_ARG(x && w_packed && w_dw && y && part, "ocv_mbconv_expand_dw_fwd: null pointer");
-  OCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "ocv_mbconv_expand_dw_fwd: bad sizes");
+  if (ocv_check_dw_geometry("ocv_mbconv_expand_dw_fwd", false, B, 0, H, W, k, stride, pad_t, pad_l, Ho, Wo,
+                            ocv_aligned16(x) && ocv_aligned16(w_packed) && ocv_aligned16(w_dw) && ocv_aligned16(bias_dw) && ocv_aligned16(y)) != 0)
+    return -1;
   OCV_CHECK_ARG(Cin >= 24 && Cin % 8 == 0 && Cin <= 64, "ocv_mbconv_expand_dw_fwd: Cin must be a multiple of 8 in [24, 64] (got %d)", Cin);
   OCV_CHECK_ARG(mid >= 4 && mid % 4 == 0, "ocv_mbconv_expand_dw_fwd: expanded channels must be a multiple of 4 (got %d)", mid);
-  OCV_CHECK_ARG((k == 3 || k == 5) && (stride == 1 || stride == 2), "ocv_mbconv_expand_dw_fwd: k must be 3 or 5 and stride 1 or 2 (got k=%d s=%d)", k, stride);
-  OCV_CHECK_ARG(pad_t >= 0 && pad_l >= 0 && pad_t < k && pad_l < k, "ocv_mbconv_expand_dw_fwd: bad padding");
-  OCV_CHECK_ARG((Ho - 1) * stride - pad_t < H && (Wo - 1) * stride - pad_l < W, "ocv_mbconv_expand_dw_fwd: output larger than the padded input allows");
-  OCV_CHECK_ARG(ocv_aligned16(x) && ocv_aligned16(w_packed) && ocv_aligned16(w_dw) && ocv_aligned16(bias_dw) && ocv_aligned16(y),
-                "ocv_mbconv_expand_dw_fwd: operands must be 16-byte aligned");
   FXArgs a{};
   a.x = x; a.be = bias_expand; a.wd = w_dw; a.bd = bias_dw; a.wp = (const __bf16*)w_packed; a.y = y; a.part = part;
   a.Cin = Cin; a.mid = mid; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.pad_t = pad_t; a.pad_l = pad_l;
@@ -280,11 +251,4 @@ int fx_run(const float* x, const void* w_packed, const float* bias_expand, const
   if (k == 3 && stride == 2) return fx_dispatch_ks<3, 2>(a, B, ks, st);
   if (k == 5 && stride == 1) return fx_dispatch_ks<5, 1>(a, B, ks, st);
   return fx_dispatch_ks<5, 2>(a, B, ks, st);
-}
-}  // namespace
-
-extern "C" int ocv_mbconv_expand_dw_fwd(const float* x, const void* w_packed, const float* bias_expand, const float* w_dw,
-                                        const float* bias_dw, float* y, float* part, int B, int H, int W, int Cin, int mid,
-                                        int k, int stride, int pad_t, int pad_l, int Ho, int Wo, ocv_stream_t stream) {
-  return fx_run(x, w_packed, bias_expand, w_dw, bias_dw, y, part, B, H, W, Cin, mid, k, stride, pad_t, pad_l, Ho, Wo, stream);
 }

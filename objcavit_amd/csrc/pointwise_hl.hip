@@ -24,17 +24,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.hpp"
-#include "../../include/objcavit_hip.h"
+#include "mbconv_tile.hpp"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(256))) float ocv_pwhl_zero_page[64];       // zero-initialised: source of out-of-range rows
 
 struct PHArgs {
   const __bf16* xhl;            // [M][2 Cp] hl32
@@ -49,33 +41,11 @@ struct PHArgs {
   int nbx, nby, col_major;
 };
 
-__device__ __forceinline__ float ph_act(float v, int act) {
-  switch (act) {
-    case OCV_ACT_RELU: return fmaxf(v, 0.f);
-    case OCV_ACT_LEAKY_RELU: return v > 0.f ? v : 0.01f * v;
-    case OCV_ACT_SILU: return fast_silu(v);
-    case OCV_ACT_SIGMOID: return fast_sigmoid(v);
-    default: return v;
-  }
-}
-
-__device__ __forceinline__ bf16x8 ph_ldb8(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-
-__device__ __forceinline__ f32x16 ph_mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  return acc;
-}
-
-constexpr int PH_TS = 32;                       // floats per LDS row of the epilogue's transpose scratch: UNPADDED -- the four
-                                                // 16-lane groups of its ds_read_b128 each cover whole 256-byte bank rows (a padded
-                                                // row of 40 floats costs 3 LDS cycles per group: MI355X_MICROARCH.md, LDS table)
-constexpr int PH_TSCRATCH = 32 * PH_TS;         // floats per wavefront
 constexpr int PH_SLABB = 256;                   // bytes per row and K slab: 64 channels = two hl32 blocks (hi | lo | hi | lo)
 
 // bias + activation (+ residual) of one 32 x 32 accumulator tile, transposed through the wavefront's own LDS scratch so
-// that it leaves as 16-byte stores of whole 128-byte row segments (pointwise_split.hip, store_tile_lds); optionally also
+// that it leaves as 16-byte stores of whole 128-byte row segments (TS, TSCRATCH: mbconv_tile.hpp; pointwise_split.hip's
+// store_tile_lds is the fp32-row kernels' form: prefetched residual, ragged channel counts); optionally also
 // as the hl32 split of the same values (two 8-byte stores per lane: hi and lo quads of the channel block).
 // rows_left = rows of the tile that exist (image / tensor end).
 __device__ __forceinline__ void ph_store_tile(const PHArgs& p, const f32x16& acc, float* scratch, long m_base, int rows_left,
@@ -86,20 +56,20 @@ __device__ __forceinline__ void ph_store_tile(const PHArgs& p, const f32x16& acc
   // (one uniform branch per tile, not a switch per element)
   if (p.act == OCV_ACT_SILU) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * PH_TS + l31] = fast_silu(acc[r] + bv);
+    for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * TS + l31] = fast_silu(acc[r] + bv);
   } else if (p.act == OCV_ACT_NONE) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * PH_TS + l31] = acc[r] + bv;
+    for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * TS + l31] = acc[r] + bv;
   } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * PH_TS + l31] = ph_act(acc[r] + bv, p.act);
+    for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * TS + l31] = ocv_act(acc[r] + bv, p.act);
   }
   const int c4 = lane & 7, ncol = n0 + 4 * c4;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int row = (lane >> 3) + 8 * it;
     const long m = m_base + row;
-    float4 v = *reinterpret_cast<const float4*>(scratch + row * PH_TS + 4 * c4);
+    float4 v = *reinterpret_cast<const float4*>(scratch + row * TS + 4 * c4);
     if (row < rows_left) {
       if (ncol < p.N) {
         if (p.res != nullptr) {
@@ -111,15 +81,9 @@ __device__ __forceinline__ void ph_store_tile(const PHArgs& p, const f32x16& acc
         v = make_float4(0.f, 0.f, 0.f, 0.f);       // pad channels of the split copy
       }
       if (p.yhl != nullptr && ncol < p.Cpo) {
-        const float f[4] = {v.x, v.y, v.z, v.w};
         bf16x4 h, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const __bf16 hb = (__bf16)f[e];
-          h[e] = hb;
-          l[e] = (__bf16)(f[e] - (float)hb);
-        }
-        __bf16* d = p.yhl + m * 2 * p.Cpo + (ncol >> 5) * 64 + (ncol & 31);
+        split4(v, h, l);
+        __bf16* d = hl_at(p.yhl, m, ncol, p.Cpo);
         *reinterpret_cast<bf16x4*>(d) = h;
         *reinterpret_cast<bf16x4*>(d + 32) = l;
       }
@@ -135,7 +99,7 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
   constexpr int BUFB = ROWS * PH_SLABB;
   constexpr int PIECES = ROWS / 4;               // LDS-DMA instructions per slab (1 KB each: 4 rows x 16 chunks)
   static_assert(NBUF >= 2 && (NBUF - 2) * PIECES <= 63, "counted vmcnt must fit its 6-bit field");
-  static_assert(NBUF * BUFB >= 4 * PH_TSCRATCH * (int)sizeof(float), "epilogue scratch aliases the slab ring");
+  static_assert(NBUF * BUFB >= 4 * TSCRATCH * (int)sizeof(float), "epilogue scratch aliases the slab ring");
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -173,7 +137,7 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
         const int row = 4 * i + lrow;
         const unsigned cb = kb + (unsigned)((cst ^ (row & 15)) * 16);
         const bool ok = row < rows_left && cb < rowb;
-        const void* src = ok ? (const void*)(xb + (long)row * rowb + cb) : (const void*)ocv_pwhl_zero_page;
+        const void* src = ok ? (const void*)(xb + (long)row * rowb + cb) : (const void*)ocv_zero_page;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + i * 1024), 16, 0, 0);
       }
     };
@@ -206,7 +170,7 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     jt[j] = (by * 4 + wave) * TN + j;
-    wf[j] = wimg + ((long)min(jt[j], ntl_all - 1) * nsteps * 2) * 512 + lane * 8;       // + step * 1024 (+ 512: lo)
+    wf[j] = w_frag(wimg, min(jt[j], ntl_all - 1), p.Kp, 0, lane);                      // + step * 1024 (+ 512: lo)
   }
   const bool any_cols = jt[0] < ntl_all;                              // a wavefront past the last channel block only keeps the barriers
 
@@ -223,8 +187,8 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
     const long o = (long)min(gs, nsteps - 1) * 1024;                 // past the end: re-read the last step (multiplies zeros)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      h[j] = ph_ldb8(wf[j] + o);
-      l[j] = ph_ldb8(wf[j] + o + 512);
+      h[j] = ldb8(wf[j] + o);
+      l[j] = ldb8(wf[j] + o + 512);
     }
   };
   load_b(0, bh[0], bl[0]);
@@ -259,7 +223,7 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) acc[rt][j] = ph_mfma3(ah[rt], al[rt], bh[s][j], bl[s][j], acc[rt][j]);
+          for (int j = 0; j < TN; ++j) acc[rt][j] = mfma3(ah[rt], al[rt], bh[s][j], bl[s][j], acc[rt][j]);
       }
     }
     // this wavefront's reads of the slab have returned (the MFMAs consumed them); release the buffer
@@ -269,7 +233,7 @@ __global__ __launch_bounds__(320) void pw_hl_kernel(PHArgs p) {
   }
   if (!any_cols) return;
   // epilogue: the ring is idle (every consumer is past the last barrier, the producer has nothing in flight)
-  float* scratch = reinterpret_cast<float*>(lds) + wave * PH_TSCRATCH;
+  float* scratch = reinterpret_cast<float*>(lds) + wave * TSCRATCH;
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -282,11 +246,7 @@ template <int RT, int TN, int NBUF>
 int launch_ph(PHArgs a, hipStream_t st) {
   constexpr int ROWS = 32 * RT;
   constexpr size_t LDS = (size_t)NBUF * ROWS * PH_SLABB;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)pw_hl_kernel<RT, TN, NBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  ocv_allow_dynamic_lds<pw_hl_kernel<RT, TN, NBUF>>();
   a.tiles_per_image = ocv_cdiv(a.rows_per_image, ROWS);
   a.nbx = (int)(a.M / a.rows_per_image) * a.tiles_per_image;
   a.nby = ocv_cdiv(a.N, 128 * TN);

@@ -23,21 +23,18 @@
 //                            end).  Rows are staged through LDS as split bf16 (converted ONCE per workgroup, coalesced
 //                            256-byte row segments), double buffered, one barrier per slab; the next slab's global
 //                            loads (rows and weights) are issued before the current slab's MFMAs.
-// In all three the weights are read straight from L2 into the B operand as contiguous 1 KB fragments (w_frag below).
+// In all three the weights are read straight from L2 into the B operand as contiguous 1 KB fragments (w_frag, mbconv_tile.hpp).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.hpp"
-#include "../../include/objcavit_hip.h"
+#include "mbconv_tile.hpp"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct PSArgs {
   const float *x, *gate, *bias, *res;
-  const __bf16* wp;                 // packed B-operand fragments, see w_frag()
+  const __bf16* wp;                 // packed B-operand fragments (w_frag, mbconv_tile.hpp)
   float* y;
   long M;
   int K, Kp, N, rows_per_image, act;
@@ -50,53 +47,6 @@ struct PSArgs {
                                     // pw_splitk_finish_kernel adds the slices in a fixed order)
 };
 
-__device__ __forceinline__ float act_fn(float v, int act) {
-  switch (act) {
-    case OCV_ACT_RELU: return fmaxf(v, 0.f);
-    case OCV_ACT_LEAKY_RELU: return v > 0.f ? v : 0.01f * v;
-    case OCV_ACT_SILU: return fast_silu(v);
-    case OCV_ACT_SIGMOID: return fast_sigmoid(v);
-    default: return v;
-  }
-}
-
-// 8 consecutive floats (two 16-byte vectors) -> bf16 hi / lo octets
-__device__ __forceinline__ void split8(const float4 u, const float4 v, bf16x8& hi, bf16x8& lo) {
-  const float f[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)f[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(f[i] - (float)h);
-  }
-}
-
-__device__ __forceinline__ float4 mul4(float4 a, const float4 g) {
-  a.x *= g.x; a.y *= g.y; a.z *= g.z; a.w *= g.w;
-  return a;
-}
-
-__device__ __forceinline__ bf16x8 ldb8(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ float4 lda4(const float* p) { return ld4(p); }
-__device__ __forceinline__ float4 ldg4(const float* p) { return ld4(p); }
-
-// Weight layout ("packed", built once on the host side of the C ABI): the B operand of v_mfma_f32_32x32x16_bf16 for
-// channel tile jt (32 channels) and K step s (16 inputs) is ONE contiguous 1 KB fragment -- lane l = 32 hh + l31
-// holds W[32 jt + l31][16 s + 8 hh .. + 7] -- hi fragment first, lo fragment right behind it:
-//   wp[((jt * nsteps + s) * 2 + part) * 512 + lane * 8 + e]
-// so a wavefront's weight load touches 8 consecutive cache lines instead of 32 scattered ones (with row-major [N][K]
-// weights the per-line tag work of those loads, not bandwidth, was the largest single cost of the tile kernel).
-__device__ __forceinline__ const __bf16* w_frag(const PSArgs& p, int jt, int s, int lane) {
-  return p.wp + (((long)jt * (p.Kp >> 4) + s) * 2) * 512 + lane * 8;
-}
-
-__device__ __forceinline__ f32x16 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  return acc;
-}
-
 // bias + activation + residual + store of one 32 x 32 accumulator tile whose first row is m_base
 __device__ __forceinline__ void store_tile(const PSArgs& p, const f32x16& acc, long m_base, int n, int hh) {
   if (n >= p.N) return;
@@ -105,7 +55,7 @@ __device__ __forceinline__ void store_tile(const PSArgs& p, const f32x16& acc, l
   for (int r = 0; r < 16; ++r) {
     const long m = m_base + acc_row(r, hh);
     if (m < p.M) {
-      float v = act_fn(acc[r] + bv, p.act);
+      float v = ocv_act(acc[r] + bv, p.act);
       if (p.res != nullptr) v += p.res[m * p.N + n];
       p.y[m * p.N + n] = v;
     }
@@ -114,13 +64,9 @@ __device__ __forceinline__ void store_tile(const PSArgs& p, const f32x16& acc, l
 
 // Coalesced epilogue.  Storing a 32 x 32 accumulator tile straight from its MFMA layout takes 16 four-byte store
 // instructions of two 128-byte runs each and is store-issue-bound (the expand layers spent as long in their stores as
-// in everything else: 24 -> 144 at 240 x 320, 269 us with and 135 us without them).  The tile is transposed through
-// 4 KB of LDS owned by the wavefront and leaves as four 16-byte-per-lane stores of 8 rows x 128 B.  Lane l owns columns
-// 4 (l & 7) .. +3 of rows (l >> 3) + 8 it.  Rows are UNPADDED (32 floats): the ds_write_b32 of a 32-lane half covers one
-// row = 32 consecutive banks, and each 16-lane group of the ds_read_b128 ({0-3, 12-15, 20-27}, ...) covers whole 256-byte
-// bank rows -- one LDS cycle per group; the 40-float rows of round 2 cost three (MI355X_MICROARCH.md, LDS table).
-constexpr int TS = 32;                          // floats per LDS row of the transpose scratch
-constexpr int TSCRATCH = 32 * TS;               // floats per wavefront
+// in everything else: 24 -> 144 at 240 x 320, 269 us with and 135 us without them).  The tile is transposed through the
+// wavefront's own scratch (TS, TSCRATCH: mbconv_tile.hpp) and leaves as four 16-byte-per-lane stores of 8 rows x 128 B.
+// Lane l owns columns 4 (l & 7) .. +3 of rows (l >> 3) + 8 it.
 
 // The residual (skip connection) of a tile in that same lane order, fetched BEFORE the K loop: read in the epilogue
 // its latency sat fully exposed at the end of every wavefront (240 -> 40 at 120 x 160: 51 of 166 us for 49 MB).
@@ -144,7 +90,7 @@ __device__ __forceinline__ void store_tile_lds(const PSArgs& p, const f32x16& ac
   const int n = n0 + l31;
   const float bv = (p.bias != nullptr && n < p.N) ? p.bias[n] : 0.f;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * TS + l31] = act_fn(acc[r] + bv, p.act);
+  for (int r = 0; r < 16; ++r) scratch[acc_row(r, hh) * TS + l31] = ocv_act(acc[r] + bv, p.act);
   const int c4 = lane & 7, ncol = n0 + 4 * c4;
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
@@ -163,18 +109,11 @@ __device__ __forceinline__ void store_tile_lds(const PSArgs& p, const f32x16& ac
       v = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (p.yhl != nullptr && ncol < p.Cpo && m < p.M) {
-      typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-      const float f[4] = {v.x, v.y, v.z, v.w};
-      bf16x4_t h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = (__bf16)f[e];
-        h[e] = hb;
-        l[e] = (__bf16)(f[e] - (float)hb);
-      }
-      __bf16* d = p.yhl + m * 2 * p.Cpo + (ncol >> 5) * 64 + (ncol & 31);
-      *reinterpret_cast<bf16x4_t*>(d) = h;
-      *reinterpret_cast<bf16x4_t*>(d + 32) = l;
+      bf16x4 h, l;
+      split4(v, h, l);
+      __bf16* d = hl_at(p.yhl, m, ncol, p.Cpo);
+      *reinterpret_cast<bf16x4*>(d) = h;
+      *reinterpret_cast<bf16x4*>(d + 32) = l;
     }
   }
 }
@@ -200,11 +139,11 @@ __global__ __launch_bounds__(256) void pw_rows_kernel(PSArgs p) {
     for (int s = 0; s < KS; ++s) {
       float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
       if (ok && 16 * s + 8 * hh < K) {
-        u = lda4(src + 16 * s);
-        v = lda4(src + 16 * s + 4);
+        u = ld4(src + 16 * s);
+        v = ld4(src + 16 * s + 4);
         if (gsrc != nullptr) {
-          u = mul4(u, ldg4(gsrc + 16 * s));
-          v = mul4(v, ldg4(gsrc + 16 * s + 4));
+          u = mul4(u, ld4(gsrc + 16 * s));
+          v = mul4(v, ld4(gsrc + 16 * s + 4));
         }
       }
       split8(u, v, ahi[s], alo[s]);
@@ -216,7 +155,7 @@ __global__ __launch_bounds__(256) void pw_rows_kernel(PSArgs p) {
   const int nt_lo = blockIdx.y * per_y, nt_hi = min(ntiles_all, nt_lo + per_y);
   for (int nt = nt_lo; nt < nt_hi; ++nt) {
     const int n = nt * 32 + l31;
-    const __bf16* wf = w_frag(p, nt, 0, lane);
+    const __bf16* wf = w_frag(p.wp, nt, p.Kp, 0, lane);
     f32x16 acc = {0};
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -263,7 +202,7 @@ __global__ __launch_bounds__(64 * WN * WK) void pw_tile_kernel(PSArgs p) {
   const long m0 = (long)bx * ROWS;
   const int n = by * (32 * WN) + wn * 32 + l31;
   const int ntl_all = (p.N + 31) >> 5;
-  const __bf16* wf = w_frag(p, min(by * WN + wn, ntl_all - 1), 4 * g, lane);      // + (it * KI / 16 + s) * 1024
+  const __bf16* wf = w_frag(p.wp, min(by * WN + wn, ntl_all - 1), p.Kp, 4 * g, lane);      // + (it * KI / 16 + s) * 1024
   const int K = p.K, Kp = p.Kp;
   const int nit_all = (Kp + KI - 1) / KI;
   const int it0 = p.ksplit > 1 ? nit_all * kz / p.ksplit : 0;           // this workgroup's K slabs [it0, nit)
@@ -292,11 +231,11 @@ __global__ __launch_bounds__(64 * WN * WK) void pw_tile_kernel(PSArgs p) {
       const int k = it * KI + akoff[i];
       ra[i][0] = ra[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (k < K && k >= 0) {
-        ra[i][0] = lda4(asrc[i] + it * KI);
-        ra[i][1] = lda4(asrc[i] + it * KI + 4);
+        ra[i][0] = ld4(asrc[i] + it * KI);
+        ra[i][1] = ld4(asrc[i] + it * KI + 4);
         if (gsrc[i] != nullptr) {
-          ra[i][0] = mul4(ra[i][0], ldg4(gsrc[i] + it * KI));
-          ra[i][1] = mul4(ra[i][1], ldg4(gsrc[i] + it * KI + 4));
+          ra[i][0] = mul4(ra[i][0], ld4(gsrc[i] + it * KI));
+          ra[i][1] = mul4(ra[i][1], ld4(gsrc[i] + it * KI + 4));
         }
       }
     }
@@ -399,11 +338,7 @@ int launch_tile(const PSArgs& a, hipStream_t st) {
   constexpr size_t STAGE = (size_t)2 * WK * 2 * ROWS * LROW;
   constexpr size_t TRANS = ((size_t)(WK - 1) * WN * RT * 16 * 64 + (size_t)WN * TSCRATCH) * sizeof(float);   // reduction slabs + scratch
   constexpr size_t LDS = STAGE > TRANS ? STAGE : TRANS;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)pw_tile_kernel<WN, WK, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  ocv_allow_dynamic_lds<pw_tile_kernel<WN, WK, RT>>();
   PSArgs b = a;
   b.nbx = (int)((a.M + ROWS - 1) / ROWS);
   b.nby = ocv_cdiv(a.N, 32 * WN);
@@ -439,7 +374,7 @@ __global__ __launch_bounds__(256) void pw_splitk_finish_kernel(PwFinArgs p) {
     a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
   }
   const float4 bv = p.bias != nullptr ? ld4(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-  a.x = act_fn(a.x + bv.x, p.act); a.y = act_fn(a.y + bv.y, p.act); a.z = act_fn(a.z + bv.z, p.act); a.w = act_fn(a.w + bv.w, p.act);
+  a.x = ocv_act(a.x + bv.x, p.act); a.y = ocv_act(a.y + bv.y, p.act); a.z = ocv_act(a.z + bv.z, p.act); a.w = ocv_act(a.w + bv.w, p.act);
   if (p.res != nullptr) {
     const float4 q = ld4(p.res + o);
     a.x += q.x; a.y += q.y; a.z += q.z; a.w += q.w;
@@ -480,7 +415,7 @@ __global__ __launch_bounds__(256) void pw_stream_kernel(PSArgs p) {
   const int ntl_all = (p.N + 31) >> 5;
   const __bf16* wf[NTL];
 #pragma unroll
-  for (int j = 0; j < NTL; ++j) wf[j] = w_frag(p, min(j, ntl_all - 1), 0, lane);
+  for (int j = 0; j < NTL; ++j) wf[j] = w_frag(p.wp, min(j, ntl_all - 1), p.Kp, 0, lane);
   f32x16 acc[NTL];
 #pragma unroll
   for (int j = 0; j < NTL; ++j) acc[j] = f32x16{0};
@@ -500,8 +435,8 @@ __global__ __launch_bounds__(256) void pw_stream_kernel(PSArgs p) {
       const int s = s0 + u;
       ra[u][0] = ra[u][1] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (16 * s < klim) {
-        ra[u][0] = lda4(src + 16 * s);
-        ra[u][1] = lda4(src + 16 * s + 4);
+        ra[u][0] = ld4(src + 16 * s);
+        ra[u][1] = ld4(src + 16 * s + 4);
       }
       if (s < nsteps) {
 #pragma unroll
@@ -516,8 +451,8 @@ __global__ __launch_bounds__(256) void pw_stream_kernel(PSArgs p) {
       for (int u = 0; u < U; ++u) {
         const int s = s0 + u;
         if (16 * s < klim) {
-          ra[u][0] = mul4(ra[u][0], ldg4(gsrc + 16 * s));
-          ra[u][1] = mul4(ra[u][1], ldg4(gsrc + 16 * s + 4));
+          ra[u][0] = mul4(ra[u][0], ld4(gsrc + 16 * s));
+          ra[u][1] = mul4(ra[u][1], ld4(gsrc + 16 * s + 4));
         }
       }
     }

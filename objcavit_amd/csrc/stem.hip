@@ -11,7 +11,6 @@
 // lifetime of the wavefront, which walks pixel tiles grid-stride.  Exact fp32.  Output rows are 128-byte (+ 64-byte)
 // contiguous runs per pixel.
 #include "common.hpp"
-#include "../../include/objcavit_hip.h"
 
 namespace {
 
@@ -86,8 +85,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(StemArgs p) {
         for (int r = 0; r < 16; ++r) {
           const long mo = tile * 32 + acc_row(r, hh);
           if (mo < p.M) {
-            float v = acc[j][r] + bv[j];
-            if (p.act == OCV_ACT_SILU) v = fast_silu(v);
+            float v = acc[j][r] + bv[j];                          // (the three codes the entry point admits, not ocv_act's five:
+            if (p.act == OCV_ACT_SILU) v = fast_silu(v);           //  the sigmoid case would be compiled into every store)
             else if (p.act == OCV_ACT_RELU) v = fmaxf(v, 0.f);
             else if (p.act == OCV_ACT_LEAKY_RELU) v = v > 0.f ? v : 0.01f * v;
             p.y[mo * p.Cout + n] = v;
@@ -195,11 +194,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wide_kernel(StemArgs p) {
           float* vv = reinterpret_cast<float*>(&v);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float x = acc[j][4 * g + e];
-            if (ACT == OCV_ACT_SILU) x = fast_silu(x);
-            else if (ACT == OCV_ACT_RELU) x = fmaxf(x, 0.f);
-            else if (ACT == OCV_ACT_LEAKY_RELU) x = x > 0.f ? x : 0.01f * x;
-            vv[e] = x;
+            vv[e] = ocv_act(acc[j][4 * g + e], ACT);
           }
           if (pix_ok) *reinterpret_cast<float4*>(p.y + (yt + 32 * j + 8 * g)) = v;
         }

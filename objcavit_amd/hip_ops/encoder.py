@@ -1,6 +1,6 @@
 """hip_ops: the EfficientNet encoder's NHWC blocks -- stem, 1x1 (split / exact / pre-split), depthwise (+ squeeze-excite pooling and
 gate), fused expand + depthwise -- and the validation metrics (csrc/stem.hip, pointwise_split.hip, pointwise_hl.hip, depthwise_se.hip,
-mbconv_fused.hip, encoder_nhwc.hip, metrics.hip).
+se_gate.hip, mbconv_fused.hip, encoder_nhwc.hip, metrics.hip).
 """
 from __future__ import annotations
 
@@ -342,6 +342,34 @@ def depthwise_nhwc_same(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optiona
     return out
 
 
+def _se_workspaces(fn: str, x: torch.Tensor, C: int, tiles: int, w1, b1, w2t, b2, named=(), what: str = "squeeze-excite parameter",
+                   want_gate: bool = True):
+    """What the three depthwise + squeeze-excite functions do between their depthwise geometry and their launches: the tensors in
+    ``named`` and the squeeze-excite parameters are fp32, contiguous and on the device, the parameters fit C channels, the
+    depthwise kernel has ``tiles`` > 0 pooling partials per image; returns (R, part [B, tiles, C], hid [B, R], gate [B, C] or None)."""
+    for n, t in tuple(named) + (("w1", w1), ("b1", b1), ("w2t", w2t), ("b2", b2)):
+        if t is not None:
+            _req(t, n)
+    R = w1.shape[0]
+    if w1.shape != (R, C) or w2t.shape != (R, C) or b1.numel() != R or b2.numel() != C:
+        raise ValueError(f"{fn}: {what} shape mismatch")
+    if tiles <= 0:
+        raise ValueError(f"{fn}: unsupported shape")
+    B = x.shape[0]
+    part = workspace(B * tiles * C * 4, x.device, "dw_part")
+    hid = workspace(B * R * 4, x.device, "se_hidden")
+    gate = torch.empty(B, C, dtype=torch.float32, device=x.device) if want_gate else None
+    return R, part, hid, gate
+
+
+def _se_gate_from_partials(lib, part, tiles: int, pixels: int, w1, b1, w2t, b2, gate, hid, R: int):
+    B, C = gate.shape
+    with timed("se_gate"):
+        check(lib.ocv_se_gate_partials_fwd(part.data_ptr(), tiles, pixels, w1.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
+                                           b2.data_ptr(), gate.data_ptr(), hid.data_ptr(), B, C, R, _stream()),
+              "ocv_se_gate_partials_fwd")
+
+
 def depthwise_se_gate(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[torch.Tensor], k: int, stride: int,
                       w1: torch.Tensor, b1: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor, padding: Optional[Tuple[int, int]] = None):
     """silu(depthwise k x k (TF 'SAME') + bias) of a channels_last tensor AND the squeeze-excite gate of that output: three
@@ -353,28 +381,15 @@ def depthwise_se_gate(x: torch.Tensor, weight_kkc: torch.Tensor, bias: Optional[
     B, Cc, H, W = x.shape
     if weight_kkc.shape != (k * k, Cc):
         raise ValueError(f"depthwise_se_gate: weight {tuple(weight_kkc.shape)} does not match k={k}, C={Cc}")
-    for n, t in (("bias", bias), ("w1", w1), ("b1", b1), ("w2t", w2t), ("b2", b2)):
-        if t is not None:
-            _req(t, n)
-    R = w1.shape[0]
-    if w1.shape != (R, Cc) or w2t.shape != (R, Cc) or b1.numel() != R or b2.numel() != Cc:
-        raise ValueError("depthwise_se_gate: squeeze-excite parameter shape mismatch")
     Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     tiles = lib.ocv_depthwise_sum_tiles(B, Cc, Ho, Wo, k, stride)
-    if tiles <= 0:
-        raise ValueError("depthwise_se_gate: unsupported shape")
+    R, part, hid, gate = _se_workspaces("depthwise_se_gate", x, Cc, tiles, w1, b1, w2t, b2, (("bias", bias),))
     out = torch.empty(B, Cc, Ho, Wo, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    part = workspace(B * tiles * Cc * 4, x.device, "dw_part")
-    gate = torch.empty(B, Cc, dtype=torch.float32, device=x.device)
-    hid = workspace(B * R * 4, x.device, "se_hidden")
     with timed(f"depthwise|{B},{H},{W},{Cc},k{k}s{stride}"):
         check(lib.ocv_depthwise_conv_nhwc_sum_fwd(x.data_ptr(), weight_kkc.data_ptr(), _ptr(bias), out.data_ptr(),
                                                   part.data_ptr(), B, Cc, H, W, k, stride, pt, pl, Ho, Wo,
                                                   _stream()), "ocv_depthwise_conv_nhwc_sum_fwd")
-    with timed("se_gate"):
-        check(lib.ocv_se_gate_partials_fwd(part.data_ptr(), tiles, Ho * Wo, w1.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
-                                           b2.data_ptr(), gate.data_ptr(), hid.data_ptr(), B, Cc, R, _stream()),
-              "ocv_se_gate_partials_fwd")
+    _se_gate_from_partials(lib, part, tiles, Ho * Wo, w1, b1, w2t, b2, gate, hid, R)
     return out, gate
 
 
@@ -390,23 +405,16 @@ def depthwise_se_gate_weights(x: torch.Tensor, weight_kkc: torch.Tensor, bias: O
     B, Cc, H, W = x.shape
     if weight_kkc.shape != (k * k, Cc) or Cc % 32 != 0:
         raise ValueError(f"depthwise_se_gate_weights: weight {tuple(weight_kkc.shape)} does not match k={k}, C={Cc} (C % 32 == 0)")
-    for n, t in (("bias", bias), ("w1", w1), ("b1", b1), ("w2t", w2t), ("b2", b2), ("w_proj", w_proj)):
-        if t is not None:
-            _req(t, n)
-    R = w1.shape[0]
-    N = w_proj.shape[0]
-    if w1.shape != (R, Cc) or w2t.shape != (R, Cc) or b1.numel() != R or b2.numel() != Cc or tuple(w_proj.shape) != (N, Cc):
-        raise ValueError("depthwise_se_gate_weights: parameter shape mismatch")
     Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     tiles = lib.ocv_depthwise_sum_tiles(B, Cc, Ho, Wo, k, stride)
-    if tiles <= 0:
-        raise ValueError("depthwise_se_gate_weights: unsupported shape")
+    R, part, hid, gate = _se_workspaces("depthwise_se_gate_weights", x, Cc, tiles, w1, b1, w2t, b2, (("bias", bias), ("w_proj", w_proj)),
+                                        what="parameter", want_gate=want_gate)
+    N = w_proj.shape[0]
+    if tuple(w_proj.shape) != (N, Cc):
+        raise ValueError("depthwise_se_gate_weights: parameter shape mismatch")
     ys = SplitAct.empty(B, Cc, Ho, Wo, x.device)
-    part = workspace(B * tiles * Cc * 4, x.device, "dw_part")
-    hid = workspace(B * R * 4, x.device, "se_hidden")
     img_elems = int(lib.ocv_pointwise_packed_weight_elems(Cc, N))
     wpk = torch.empty(B * img_elems, dtype=torch.bfloat16, device=x.device)
-    gate = torch.empty(B, Cc, dtype=torch.float32, device=x.device) if want_gate else None
     with timed(f"depthwise|{B},{H},{W},{Cc},k{k}s{stride}"):
         check(lib.ocv_depthwise_conv_nhwc_sum_hl_fwd(x.data_ptr(), weight_kkc.data_ptr(), _ptr(bias), None, ys.hl.data_ptr(),
                                                      part.data_ptr(), B, Cc, H, W, k, stride, pt, pl, Ho, Wo,
@@ -443,30 +451,17 @@ def expand_depthwise_se_gate(x: torch.Tensor, w_expand: "SplitWeight", b_expand:
     _req(weight_kkc, "weight")
     if weight_kkc.shape != (k * k, mid):
         raise ValueError(f"expand_depthwise_se_gate: depthwise weight {tuple(weight_kkc.shape)} does not match k={k}, C={mid}")
-    for n, t in (("b_expand", b_expand), ("bias", bias), ("w1", w1), ("b1", b1), ("w2t", w2t), ("b2", b2)):
-        if t is not None:
-            _req(t, n)
-    R = w1.shape[0]
-    if w1.shape != (R, mid) or w2t.shape != (R, mid) or b1.numel() != R or b2.numel() != mid:
-        raise ValueError("expand_depthwise_se_gate: squeeze-excite parameter shape mismatch")
-    if (b_expand is not None and b_expand.numel() != mid) or (bias is not None and bias.numel() != mid):
-        raise ValueError("expand_depthwise_se_gate: bias size mismatch")
     Ho, Wo, pt, pl = _out_pad(H, W, k, stride, padding)
     tiles = lib.ocv_mbconv_expand_dw_tiles(Ho, Wo, k, stride)
-    if tiles <= 0:
-        raise ValueError("expand_depthwise_se_gate: unsupported shape")
+    R, part, hid, gate = _se_workspaces("expand_depthwise_se_gate", x, mid, tiles, w1, b1, w2t, b2, (("b_expand", b_expand), ("bias", bias)))
+    if (b_expand is not None and b_expand.numel() != mid) or (bias is not None and bias.numel() != mid):
+        raise ValueError("expand_depthwise_se_gate: bias size mismatch")
     out = torch.empty(B, mid, Ho, Wo, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    part = workspace(B * tiles * mid * 4, x.device, "dw_part")
-    gate = torch.empty(B, mid, dtype=torch.float32, device=x.device)
-    hid = workspace(B * R * 4, x.device, "se_hidden")
     with timed(f"expand_dw|{B},{H},{W},{Cin},{mid},k{k}s{stride}"):
         check(lib.ocv_mbconv_expand_dw_fwd(x.data_ptr(), w_expand.packed.data_ptr(), _ptr(b_expand), weight_kkc.data_ptr(),
                                            _ptr(bias), out.data_ptr(), part.data_ptr(), B, H, W, Cin, mid, k, stride,
                                            pt, pl, Ho, Wo, _stream()), "ocv_mbconv_expand_dw_fwd")
-    with timed("se_gate"):
-        check(lib.ocv_se_gate_partials_fwd(part.data_ptr(), tiles, Ho * Wo, w1.data_ptr(), b1.data_ptr(), w2t.data_ptr(),
-                                           b2.data_ptr(), gate.data_ptr(), hid.data_ptr(), B, mid, R, _stream()),
-              "ocv_se_gate_partials_fwd")
+    _se_gate_from_partials(lib, part, tiles, Ho * Wo, w1, b1, w2t, b2, gate, hid, R)
     return out, gate
 
 

@@ -17,7 +17,7 @@ Inference plan on the GPU (eval + no_grad): every
 BatchNorm is folded into the preceding convolution once and cached per
 parameter version; stem, 1x1 expand / project (+ gate + skip), depthwise
 (+ squeeze-excite pooling) and the gate all run as hand-written NHWC HIP
-kernels (csrc/stem.hip, pointwise_split.hip, depthwise_se.hip,
+kernels (csrc/stem.hip, pointwise_split.hip, depthwise_se.hip, se_gate.hip,
 mbconv_fused.hip) -- nothing of the encoder reaches MIOpen / hipBLASLt.  In
 training mode or on the CPU the plain PyTorch module graph runs (that is also
 what the golden generator wraps in the reference's ``Encoder``).

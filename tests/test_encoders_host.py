@@ -159,3 +159,47 @@ def test_strided_conv_argument_validation_on_the_host():
     assert call(Ho=6) == -1 and b"output larger" in lib.ocv_last_error()
     assert call(Cin=22) == -1 and b"multiple of 4" in lib.ocv_last_error()
     assert call(act=7) == -1 and b"activation" in lib.ocv_last_error()
+
+
+def test_depthwise_argument_validation_on_the_host():
+    """The three depthwise entry points share one geometry check; each keeps its own prefix, and a channel count of 0 (or any
+    that is no multiple of 4) is an argument error of the two that walk channels in quads, never a launch."""
+    if not os.path.exists(_lib.LIB_PATH):
+        from objcavit_amd.build import build
+        build()
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(4096 + 16)
+    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 16          # a 16-byte aligned host address: never dereferenced
+
+    def plain(B=1, C=8, H=8, W=8, k=3, s=1, pt=1, pl=1, Ho=8, Wo=8, act=0, x=p):
+        return lib.ocv_depthwise_conv_nhwc_fwd(x, p, None, p, B, C, H, W, k, s, pt, pl, Ho, Wo, act, None)
+
+    def summed(B=1, C=8, H=8, W=8, k=3, s=1, pt=1, pl=1, Ho=8, Wo=8, x=p):
+        return lib.ocv_depthwise_conv_nhwc_sum_fwd(x, p, None, p, p, B, C, H, W, k, s, pt, pl, Ho, Wo, None)
+
+    def summed_hl(B=1, C=32, H=8, W=8, k=3, s=1, pt=1, pl=1, Ho=8, Wo=8, x=p):
+        return lib.ocv_depthwise_conv_nhwc_sum_hl_fwd(x, p, None, None, p, p, B, C, H, W, k, s, pt, pl, Ho, Wo, None)
+
+    def fused(B=1, H=8, W=8, Cin=24, mid=144, k=3, s=1, pt=1, pl=1, Ho=8, Wo=8, x=p):
+        return lib.ocv_mbconv_expand_dw_fwd(x, p, None, p, None, p, p, B, H, W, Cin, mid, k, s, pt, pl, Ho, Wo, None)
+
+    for call, prefix in ((plain, b"ocv_depthwise_conv_nhwc_fwd: "), (summed, b"ocv_depthwise_conv_nhwc_sum_fwd: "),
+                         (summed_hl, b"ocv_depthwise_conv_nhwc_sum_fwd: ")):
+        for kw in (dict(C=0), dict(C=-4), dict(C=3), dict(C=6), dict(B=0), dict(H=0), dict(Wo=0)):
+            if call is summed_hl and kw.get("C", 0) % 32 != 0:          # the split output's own check (C % 32) comes first
+                continue
+            assert call(**kw) == -1 and lib.ocv_last_error() == prefix + b"bad sizes (C must be a multiple of 4)", kw
+    for call, prefix in ((plain, b"ocv_depthwise_conv_nhwc_fwd: "), (summed, b"ocv_depthwise_conv_nhwc_sum_fwd: "),
+                         (fused, b"ocv_mbconv_expand_dw_fwd: ")):
+        assert call(x=None) == -1 and lib.ocv_last_error() == prefix + b"null pointer"
+        assert call(k=4) == -1 and lib.ocv_last_error().startswith(prefix + b"k must be 3 or 5 and stride 1 or 2")
+        assert call(s=3) == -1 and lib.ocv_last_error().startswith(prefix + b"k must be 3 or 5 and stride 1 or 2")
+        assert call(pt=3) == -1 and lib.ocv_last_error() == prefix + b"bad padding"
+        assert call(pl=-1) == -1 and lib.ocv_last_error() == prefix + b"bad padding"
+        assert call(Ho=10) == -1 and lib.ocv_last_error() == prefix + b"output larger than the padded input allows"
+        assert call(x=p + 4) == -1 and lib.ocv_last_error() == prefix + b"operands must be 16-byte aligned"
+    assert plain(act=2) == -1 and b"activation must be none or SiLU" in lib.ocv_last_error()
+    assert summed_hl(C=8) == -1 and b"multiple of 32" in lib.ocv_last_error()
+    assert fused(B=0) == -1 and lib.ocv_last_error() == b"ocv_mbconv_expand_dw_fwd: bad sizes"
+    assert fused(Cin=20) == -1 and b"Cin must be a multiple of 8 in [24, 64] (got 20)" in lib.ocv_last_error()
+    assert fused(mid=0) == -1 and b"expanded channels must be a multiple of 4 (got 0)" in lib.ocv_last_error()

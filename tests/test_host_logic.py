@@ -505,3 +505,29 @@ def test_map_placeholder_and_fp32_map_on_the_host():
         assert float((full - x).abs().max() / x.abs().max()) < tol
     real = torch.randn(1, 8, 2, 2)
     assert hip_ops.fp32_map(real) is real
+
+
+def test_diagnostic_patches_match_the_product_sources():
+    """tools/build_variant.sh applies every tools/diag/*.patch to a copy of objcavit_amd/csrc: each hunk's old lines (context
+    and removed) must stand in today's source as one run of lines, so a change to the sources that leaves a patch behind fails here."""
+    import glob
+    patches = sorted(glob.glob(os.path.join(ROOT, "tools", "diag", "*.patch")))
+    assert patches
+    for path in patches:
+        target, old, hunks = None, [], []
+        for line in open(path).read().splitlines() + ["@@ end"]:
+            if line.startswith("--- "):
+                continue
+            if line.startswith("+++ ") or line.startswith("@@"):
+                if old:
+                    hunks.append((target, old))
+                old = []
+                if line.startswith("+++ "):
+                    target = line[4:].split("\t")[0].split("/", 1)[1]          # "b/NAME": -p1
+            elif line[:1] in (" ", "-") or line == "":
+                old.append(line[1:])
+        assert hunks, path
+        for target, old in hunks:
+            src = open(os.path.join(ROOT, "objcavit_amd", "csrc", target)).read().splitlines()
+            n = len(old)
+            assert any(src[i:i + n] == old for i in range(len(src) - n + 1)), (os.path.basename(path), target, old[:3])

@@ -7,7 +7,8 @@ Each source is compiled with the product flags of objcavit_amd/build.py plus ``-
 Columns: VGPRs AGPRs SGPRs scratch[B/lane] static-LDS[B] occupancy[waves/SIMD] (the assembly's kernel metadata) | instructions,
 matrix instructions, LDS reads, LDS writes, vector-memory loads, vector-memory stores, s_barrier, s_waitcnt | SHA-1 of the
 instruction stream with labels, comments and directives stripped (branch targets keep their number within the function, not the
-function's index in its file, so a kernel that moves to another file keeps its SHA).
+function's index in its file, so a kernel that moves to another file keeps its SHA; a symbol addressed pc-relative -- a zero page,
+say -- counts as SYM, so renaming it is not another stream).
 
     python tools/kernel_table.py --compare PARENT.txt NEW.txt       compares two saved tables by kernel name
     python tools/kernel_table.py --stream KERNEL SOURCE.hip         the stripped stream of one kernel, to diff two versions of it
@@ -55,7 +56,7 @@ def kernels(asm):
             line = line.split(";")[0].strip()
             if not line or line.endswith(":") or line.startswith("."):
                 continue
-            stream.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", line)))
+            stream.append(re.sub(r"[\w$.]+@(gotpcrel32|rel32)", r"SYM@\1", re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", line))))
         row = {"vgpr": int(f["vgpr_count"]), "agpr": int(f["agpr_count"]), "sgpr": int(f["sgpr_count"]),
                "scratch": int(f["private_segment_fixed_size"]), "lds": int(f["group_segment_fixed_size"]),
                "occ": int(occ.group(1)) if occ else -1, "insts": len(stream)}

@@ -1,4 +1,7 @@
-"""Per-shape launch timings of the NHWC encoder (pointwise / depthwise / everything else by torch.profiler)."""
+"""Per-shape launch timings of the NHWC encoder (pointwise / depthwise / everything else by torch.profiler).
+
+    python tools/prof_enc.py [BATCH]        (default 16; the library under OCV_LIB_PATH)
+"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -6,7 +9,7 @@ from objcavit_amd import hip_ops
 from objcavit_amd.config import make_args
 from objcavit_amd.modules.DenseFeatureExtractor import DenseFeatureExtractor
 torch.set_grad_enabled(False)
-B = 16
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 m = DenseFeatureExtractor(make_args()).eval().cuda()
 x = torch.randn(B, 3, 480, 640, device="cuda")
 for _ in range(2): m.encoder(x)
