@@ -718,6 +718,49 @@ int ocv_frame_resize_supported(int Hw, int Ww, int H, int W);
 int ocv_frame_resize_ingest(const uint8_t* frames, long frame_stride, long row_stride, int Hs, int Ws, int top, int left, int Hw, int Ww,
                             const float* table, const int* ystart, const float* yweight, int Ky, const int* xstart, const float* xweight,
                             int Kx, float* out, int B, int H, int W, int mirror_too, long mirror_offset, ocv_stream_t stream);
+/* Pixel formats on ingest: the two launches above for frames as decoders and capture APIs deliver them, and the window as RGB24.
+ * A frame batch is up to three PLANES, each with its own base pointer, frame stride and row stride in BYTES, at any alignment
+ * (Hc = ceil(Hs / 2), Wc = ceil(Ws / 2)); unused planes are null with strides 0:
+ *   OCV_PIXFMT_RGB24 / BGR24     plane 0 [B][Hs][Ws][3]
+ *   OCV_PIXFMT_RGBA32 / BGRA32   plane 0 [B][Hs][Ws][4], alpha ignored
+ *   OCV_PIXFMT_NV12              plane 0 = Y [B][Hs][Ws]; plane 1 = CbCr [B][Hc][Wc][2] (Cb first)
+ *   OCV_PIXFMT_I420              plane 0 = Y; plane 1 = Cb [B][Hc][Wc]; plane 2 = Cr [B][Hc][Wc]
+ * 4:2:0: pixel (x, y) takes chroma sample (x >> 1, y >> 1) (replication; no sited interpolation).  YCbCr -> RGB is STATEMENT P, in
+ * integers, from yuv_table = int32 [5][256] in device memory, made by the host in float64 and rounded once
+ * (objcavit_amd.pixel_formats.yuv_tables; matrix bt601 Kr = 0.299, Kb = 0.114 or bt709 Kr = 0.2126, Kb = 0.0722, Kg = 1 - Kr - Kb; range
+ * limited y0 = 16, sy = 255 / 219, sc = 255 / 224 or full y0 = 0, sy = sc = 1):
+ *   T0[v] = rint(2^16 sy (v - y0)) + 2^15            T1[v] = rint(2^16 sc 2 (1 - Kr) (v - 128))
+ *   T2[v] = rint(2^16 sc (-2 Kb (1 - Kb) / Kg) (v - 128))   T3[v] = rint(2^16 sc (-2 Kr (1 - Kr) / Kg) (v - 128))
+ *   T4[v] = rint(2^16 sc 2 (1 - Kb) (v - 128))
+ *   R = clamp((T0[Y] + T1[Cr]) >> 16)   G = clamp((T0[Y] + T2[Cb] + T3[Cr]) >> 16)   B = clamp((T0[Y] + T4[Cb]) >> 16)
+ * with >> the arithmetic shift and clamp to 0 .. 255.  The kernels decide no coefficient; packed formats take yuv_table = null.
+ * ocv_frame_ingest_format: ocv_frame_ingest_fwd on those R, G, B bytes -- same table, out, mirror_too, mirror_offset, the same 16-byte /
+ *   scalar store rule, one launch, no workspace (hipGraph-capturable); RGB24 launches the very kernel of ocv_frame_ingest_fwd.
+ * ocv_frame_resize_ingest_format: ocv_frame_resize_ingest likewise; only the staging step reads the format (it leaves RGB bytes in LDS),
+ *   the two tap passes are those of ocv_frame_resize_ingest: bit-equal to it on the converted frames.  Same ratio and tap limits.
+ * ocv_frames_to_rgb24: the Hw x Ww window at (top, left) -> out uint8 [B][Hw][Ww][3], every byte written, one launch.
+ * -1 before any launch, the message naming the entry point: null plane of the format, unknown format id, bad sizes, window outside the
+ * frame, a plane's strides smaller than its row (Ws x 1 / 3 / 4 bytes; chroma rows 2 Wc for NV12, Wc for I420) / its frame, null or
+ * misaligned yuv_table for a 4:2:0 format, and the out / table / tap-table / mirror checks of the rgb24 entry points.
+ * NAMES: like ocv_frame_resize_ingest these do not end in _fwd; their guarded runs are in tests/test_hip_pixel_formats.py. */
+#define OCV_PIXFMT_RGB24 0
+#define OCV_PIXFMT_BGR24 1
+#define OCV_PIXFMT_RGBA32 2
+#define OCV_PIXFMT_BGRA32 3
+#define OCV_PIXFMT_NV12 4
+#define OCV_PIXFMT_I420 5
+int ocv_frame_ingest_format(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1,
+                            long frame_stride1, long row_stride1, const uint8_t* plane2, long frame_stride2, long row_stride2,
+                            const int* yuv_table, int Hs, int Ws, int top, int left, const float* table, float* out, int B, int H, int W,
+                            int mirror_too, long mirror_offset, ocv_stream_t stream);
+int ocv_frame_resize_ingest_format(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1,
+                                   long frame_stride1, long row_stride1, const uint8_t* plane2, long frame_stride2, long row_stride2,
+                                   const int* yuv_table, int Hs, int Ws, int top, int left, int Hw, int Ww, const float* table,
+                                   const int* ystart, const float* yweight, int Ky, const int* xstart, const float* xweight, int Kx,
+                                   float* out, int B, int H, int W, int mirror_too, long mirror_offset, ocv_stream_t stream);
+int ocv_frames_to_rgb24(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1, long frame_stride1,
+                        long row_stride1, const uint8_t* plane2, long frame_stride2, long row_stride2, const int* yuv_table, int Hs, int Ws,
+                        int top, int left, uint8_t* out, int B, int Hw, int Ww, ocv_stream_t stream);
 /* Predict path, output end(modules/GraphBinsLM.py:159-183,295-301,367, metrics/MetricsPreprocess.py:17-24): the map the metric pass
  * above forms per pixel, written out.  pred [B][1][h][w], pred_mirror nullable and still mirrored (as for the metric pass):
  *   d = resize_{H x W, bilinear, align_corners}(0.5 (clamp(pred) + clamp(flip(pred_mirror)))  or  clamp(pred)), nan -> min_depth,

@@ -128,6 +128,14 @@ PROTOTYPES = {
     "ocv_frame_resize_supported": (C.c_int, [C.c_int] * 4),
     "ocv_frame_resize_ingest": (C.c_int, [_u8p, C.c_long, C.c_long] + [C.c_int] * 6 + [_f32p, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p,
                                           C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, _stream]),
+    # pixel formats on ingest: format id, three planes (pointer, frame stride, row stride in bytes), the int32 [5][256] YCbCr tables
+    "ocv_frame_ingest_format": (C.c_int, [C.c_int] + [_u8p, C.c_long, C.c_long] * 3 + [C.c_void_p] + [C.c_int] * 4 + [_f32p, _f32p, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_long, _stream]),
+    "ocv_frame_resize_ingest_format": (C.c_int, [C.c_int] + [_u8p, C.c_long, C.c_long] * 3 + [C.c_void_p] + [C.c_int] * 6 +
+                                       [_f32p, C.c_void_p, _f32p, C.c_int, C.c_void_p, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_long, _stream]),
+    "ocv_frames_to_rgb24": (C.c_int, [C.c_int] + [_u8p, C.c_long, C.c_long] * 3 + [C.c_void_p] + [C.c_int] * 4 + [_u8p, C.c_int, C.c_int,
+                                      C.c_int, _stream]),
     "ocv_depth_finalize_fwd": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, C.c_void_p, C.c_float,
                                          _u8p, _u8p, C.c_float, C.c_float, C.c_int, _stream]),
     "ocv_depth_finalize_stats_fwd": (C.c_int, [_f32p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_int,

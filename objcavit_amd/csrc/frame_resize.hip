@@ -15,17 +15,21 @@
 // tap counts so that the LDS request stays under FRAME_RESIZE_LDS_BUDGET.  Every staged extent is clamped to the window and to the LDS
 // capacity the host sized, and every LDS index to the staged extent: a zero-weight slot -- or a table that is not resize_taps' -- reads
 // a staged byte with weight 0 (or a wrong staged byte), never memory outside the window.
+// Pixel formats (ocv_frame_resize_ingest_format; pixel_fetch.hpp): frames in bgr24 / rgba32 / bgra32 / nv12 / i420 are converted while
+// they are staged -- the staged rows hold RGB bytes either way -- and the two passes do not know the difference.
 #include "common.hpp"
 #include "../../include/objcavit_hip.h"
+#include "pixel_fetch.hpp"
 
 namespace {
 
 constexpr int FRAME_RESIZE_LDS_BUDGET = 48 * 1024;    // preferred request: three workgroups per CU
 constexpr int FRAME_RESIZE_LDS_MAX = 64 * 1024;       // what one workgroup may ask for
 
+// S: pixfmt::Packed (one plane; ocv_frame_resize_ingest's arguments, in their order) or pixfmt::Planar (4:2:0 planes + the YCbCr tables)
+template <class S>
 struct ResizeArgs {
-  const uint8_t* src;
-  long frame_stride, row_stride;      // bytes
+  S s;
   const float* table;                 // [3][256]
   const int* ystart;                  // [H]
   const float* ywt;                   // [H][Ky]
@@ -40,15 +44,16 @@ struct ResizeArgs {
 
 __host__ __device__ inline int round4(int v) { return (v + 3) & ~3; }
 
-// LDS carve, in 4-byte words, every offset a multiple of 4 words (16 bytes): table | x weights | y weights | x starts | y starts |
-// fp32 tile [sr_cap][3][TW] | staged bytes [sr_cap][pw dwords]
+// LDS carve, in 4-byte words, every offset a multiple of 4 words (16 bytes): table | (4:2:0 formats: the five int32 tables of Statement
+// P, yuv_words = pixfmt::YUV_TABLE_WORDS) | x weights | y weights | x starts | y starts | fp32 tile [sr_cap][3][TW] | staged bytes
+// [sr_cap][pw dwords]
 struct Carve {
   int xw, yw, xs, ys, mid, raw, words;
 };
 
-__host__ __device__ inline Carve carve(int TH, int TW, int Ky, int Kx, int sr_cap, int pw) {
+__host__ __device__ inline Carve carve(int TH, int TW, int Ky, int Kx, int sr_cap, int pw, int yuv_words) {
   Carve c;
-  c.xw = 768;
+  c.xw = 768 + yuv_words;
   c.yw = c.xw + round4(TW * Kx);
   c.xs = c.yw + round4(TH * Ky);
   c.ys = c.xs + round4(TW);
@@ -60,11 +65,16 @@ __host__ __device__ inline Carve carve(int TH, int TW, int Ky, int Kx, int sr_ca
 
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-template <bool VEC, bool MIRROR>
-__global__ __launch_bounds__(256) void frame_resize_kernel(ResizeArgs p) {
+// FMT: the OCV_PIXFMT_* layout of the source (pixel_fetch.hpp).  Only the staging step reads it: for anything but rgb24 it leaves RGB
+// BYTES in the staged rows -- Statement P per staged pixel, or the packed format's bytes re-ordered -- at phase 0 and the same pitch, and
+// pass 1 and pass 2 run on them as they do on rgb24 bytes: same taps, same fma order.
+template <int FMT, bool VEC, bool MIRROR>
+__global__ __launch_bounds__(256) void frame_resize_kernel(ResizeArgs<typename pixfmt::Source<FMT>::type> p) {
+  constexpr bool RGB24 = FMT == OCV_PIXFMT_RGB24;
+  constexpr int YUV_WORDS = pixfmt::is_yuv(FMT) ? pixfmt::YUV_TABLE_WORDS : 0;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int TH = 1 << p.th_shift, TW = 1 << p.tw_shift;
-  const Carve cv = carve(TH, TW, p.Ky, p.Kx, p.sr_cap, p.pw);
+  const Carve cv = carve(TH, TW, p.Ky, p.Kx, p.sr_cap, p.pw, YUV_WORDS);
   float* tab = smem;
   float* xw = smem + cv.xw;
   float* yw = smem + cv.yw;
@@ -83,6 +93,10 @@ __global__ __launch_bounds__(256) void frame_resize_kernel(ResizeArgs p) {
   const int SR = min(clampi(p.ystart[ty0 + ny - 1] + p.Ky, r0 + 1, p.Hw) - r0, p.sr_cap);
 
   for (int i = tid; i < 3 * 256; i += 256) tab[i] = p.table[i];
+  if constexpr (pixfmt::is_yuv(FMT)) {
+    for (int i = tid; i < YUV_WORDS; i += 256) reinterpret_cast<int*>(smem + 768)[i] = p.s.yuv[i];
+    __syncthreads();                                            // the staging below reads the tables
+  }
   for (int i = tid; i < nx * p.Kx; i += 256) xw[i] = p.xwt[(long)tx0 * p.Kx + i];
   for (int i = tid; i < ny * p.Ky; i += 256) yw[i] = p.ywt[(long)ty0 * p.Ky + i];
   if (tid < nx) xs[tid] = p.xstart[tx0 + tid];
@@ -90,10 +104,39 @@ __global__ __launch_bounds__(256) void frame_resize_kernel(ResizeArgs p) {
 
   // stage: a wave per source row; dword k of a row covers the row's bytes 4 k - phase .. + 3 (phase = the row address mod 4), so a
   // dword that lies wholly inside the row is an aligned 4-byte load and lands on an aligned LDS dword
-  const uint8_t* base = p.src + b * p.frame_stride + (long)(p.top + r0) * p.row_stride + (long)(p.left + c0) * 3;
+  const uint8_t* base = p.s.src + b * p.s.frame_stride + (long)(p.top + r0) * p.s.row_stride + (long)(p.left + c0) * 3;    // (rgb24 only)
   const int L = SC * 3;
+  if constexpr (!RGB24) {
+    // a wave per source row, a lane per group of four staged pixels: 12 RGB bytes = dwords 3 k .. 3 k + 2 of the row; the ragged end
+    // (SC % 4 pixels) pixel by pixel through byte stores.  Nothing outside the staged extent -- hence the window -- is read.
+    const int* yt = reinterpret_cast<const int*>(smem + 768);
+    const int groups = SC >> 2;
+    for (int r = tid >> 6; r < SR; r += 4) {
+      uint32_t* row = raw + r * p.pw;
+      for (int k = tid & 63; k < groups; k += 64) {
+        uint8_t px[12];
+        pixfmt::fetch4<FMT>(p.s, yt, b, p.top + r0 + r, p.left + c0 + 4 * k, px);
+        uint32_t w[3];
+        __builtin_memcpy(w, px, 12);
+        row[3 * k] = w[0];
+        row[3 * k + 1] = w[1];
+        row[3 * k + 2] = w[2];
+      }
+      for (int k = 4 * groups + (tid & 63); k < SC; k += 64) {
+        uint8_t rgb[3];
+        pixfmt::fetch1<FMT>(p.s, yt, b, p.top + r0 + r, p.left + c0 + k, rgb);
+        uint8_t* d = reinterpret_cast<uint8_t*>(row) + 3 * k;
+        d[0] = rgb[0];
+        d[1] = rgb[1];
+        d[2] = rgb[2];
+      }
+    }
+  }
+  // rgb24: the statements of the kernel as it was, word for word (`base` and `p.s.row_stride` are read under both source types so that
+  // they need no wrapper: this instantiation's instruction stream is pinned, and the compiler's schedule follows the source closely)
+  if constexpr (RGB24)
   for (int r = tid >> 6; r < SR; r += 4) {
-    const uint8_t* rowp = base + (long)r * p.row_stride;
+    const uint8_t* rowp = base + (long)r * p.s.row_stride;
     const int phase = (int)(reinterpret_cast<uintptr_t>(rowp) & 3);
     const int ndw = (phase + L + 3) >> 2;                       // <= pw = (3 * sc_cap + 3) / 4 + 1
     for (int k = tid & 63; k < ndw; k += 64) {
@@ -114,7 +157,8 @@ __global__ __launch_bounds__(256) void frame_resize_kernel(ResizeArgs p) {
   for (int it = tid; it < (SR << p.tw_shift); it += 256) {
     const int r = it >> p.tw_shift, x = it & (TW - 1);
     if (x >= nx) continue;
-    const int phase = (int)(reinterpret_cast<uintptr_t>(base + (long)r * p.row_stride) & 3);
+    int phase = (int)(reinterpret_cast<uintptr_t>(base + (long)r * p.s.row_stride) & 3);
+    if constexpr (!RGB24) phase = 0;
     const uint8_t* rb = reinterpret_cast<const uint8_t*>(raw + r * p.pw) + phase;
     const int s0 = xs[x] - c0;
     const float* w = xw + x * p.Kx;
@@ -184,7 +228,7 @@ struct Plan {
 };
 
 // the largest tile whose LDS request stays under the budget: 8 x 64 up to a ratio of about 2.5 per axis, smaller beyond
-bool plan_tile(int Hw, int Ww, int H, int W, int Ky, int Kx, Plan* out) {
+bool plan_tile(int Hw, int Ww, int H, int W, int Ky, int Kx, Plan* out, int yuv_words = 0) {
   static const int shapes[4][2] = {{3, 6}, {3, 5}, {2, 5}, {2, 4}};
   for (int i = 0; i < 4; ++i) {
     Plan pl;
@@ -194,7 +238,7 @@ bool plan_tile(int Hw, int Ww, int H, int W, int Ky, int Kx, Plan* out) {
     pl.sr_cap = staged_extent(Hw, H, TH, Ky);
     pl.sc_cap = staged_extent(Ww, W, TW, Kx);
     pl.pw = (pl.sc_cap * 3 + 3) / 4 + 1;
-    pl.lds_bytes = carve(TH, TW, Ky, Kx, pl.sr_cap, pl.pw).words * 4;
+    pl.lds_bytes = carve(TH, TW, Ky, Kx, pl.sr_cap, pl.pw, yuv_words).words * 4;
     if (pl.lds_bytes <= FRAME_RESIZE_LDS_BUDGET || (i == 3 && pl.lds_bytes <= FRAME_RESIZE_LDS_MAX)) {
       *out = pl;
       return true;
@@ -234,16 +278,90 @@ extern "C" int ocv_frame_resize_ingest(const uint8_t* frames, long frame_stride,
                 "ocv_frame_resize_ingest: the mirrored half overlaps the batch (mirror_offset is in elements, |offset| >= B * 3 * H * W)");
   Plan pl;
   OCV_CHECK_ARG(plan_tile(Hw, Ww, H, W, Ky, Kx, &pl), "ocv_frame_resize_ingest: no tile fits %d bytes of LDS", FRAME_RESIZE_LDS_MAX);
-  ResizeArgs a{frames, frame_stride, row_stride, table, ystart, yweight, xstart, xweight, out, mirror_offset,
+  ResizeArgs<pixfmt::Packed> a{{frames, frame_stride, row_stride}, table, ystart, yweight, xstart, xweight, out, mirror_offset,
                top, left, Hw, Ww, H, W, Ky, Kx, pl.th_shift, pl.tw_shift, pl.sr_cap, pl.sc_cap, pl.pw};
   const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (!mirror_too || (mirror_offset & 3) == 0);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((W + (1 << pl.tw_shift) - 1) >> pl.tw_shift, (H + (1 << pl.th_shift) - 1) >> pl.th_shift, B);
   OCV_CHECK_ARG(grid.y <= 65535, "ocv_frame_resize_ingest: H = %d is more than 65535 tiles tall", H);
-  if (vec && mirror_too) hipLaunchKernelGGL((frame_resize_kernel<true, true>), grid, dim3(256), pl.lds_bytes, st, a);
-  else if (vec) hipLaunchKernelGGL((frame_resize_kernel<true, false>), grid, dim3(256), pl.lds_bytes, st, a);
-  else if (mirror_too) hipLaunchKernelGGL((frame_resize_kernel<false, true>), grid, dim3(256), pl.lds_bytes, st, a);
-  else hipLaunchKernelGGL((frame_resize_kernel<false, false>), grid, dim3(256), pl.lds_bytes, st, a);
+  if (vec && mirror_too) hipLaunchKernelGGL((frame_resize_kernel<OCV_PIXFMT_RGB24, true, true>), grid, dim3(256), pl.lds_bytes, st, a);
+  else if (vec) hipLaunchKernelGGL((frame_resize_kernel<OCV_PIXFMT_RGB24, true, false>), grid, dim3(256), pl.lds_bytes, st, a);
+  else if (mirror_too) hipLaunchKernelGGL((frame_resize_kernel<OCV_PIXFMT_RGB24, false, true>), grid, dim3(256), pl.lds_bytes, st, a);
+  else hipLaunchKernelGGL((frame_resize_kernel<OCV_PIXFMT_RGB24, false, false>), grid, dim3(256), pl.lds_bytes, st, a);
   OCV_CHECK_LAUNCH("ocv_frame_resize_ingest");
+  return 0;
+}
+
+namespace {
+
+struct ResizeCall {
+  const float* table;
+  const int* ystart;
+  const float* ywt;
+  const int* xstart;
+  const float* xwt;
+  float* out;
+  long mirror_offset;
+  int top, left, Hw, Ww, H, W, Ky, Kx;
+};
+
+template <int FMT>
+void launch_resize(const pixfmt::Planes& pl, const int* yuv, const ResizeCall& c, const Plan& p, bool vec, bool mirror, dim3 grid,
+                   hipStream_t st) {
+  using S = typename pixfmt::Source<FMT>::type;
+  S src;
+  if constexpr (pixfmt::is_yuv(FMT)) src = pixfmt::planar_of(pl, yuv);
+  else src = pixfmt::packed_of(pl);
+  ResizeArgs<S> a{src, c.table, c.ystart, c.ywt, c.xstart, c.xwt, c.out, c.mirror_offset, c.top, c.left, c.Hw, c.Ww, c.H, c.W, c.Ky, c.Kx,
+                  p.th_shift, p.tw_shift, p.sr_cap, p.sc_cap, p.pw};
+  if (vec && mirror) hipLaunchKernelGGL((frame_resize_kernel<FMT, true, true>), grid, dim3(256), p.lds_bytes, st, a);
+  else if (vec) hipLaunchKernelGGL((frame_resize_kernel<FMT, true, false>), grid, dim3(256), p.lds_bytes, st, a);
+  else if (mirror) hipLaunchKernelGGL((frame_resize_kernel<FMT, false, true>), grid, dim3(256), p.lds_bytes, st, a);
+  else hipLaunchKernelGGL((frame_resize_kernel<FMT, false, false>), grid, dim3(256), p.lds_bytes, st, a);
+}
+
+}  // namespace
+
+extern "C" int ocv_frame_resize_ingest_format(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1,
+                                              long frame_stride1, long row_stride1, const uint8_t* plane2, long frame_stride2,
+                                              long row_stride2, const int* yuv_table, int Hs, int Ws, int top, int left, int Hw, int Ww,
+                                              const float* table, const int* ystart, const float* yweight, int Ky, const int* xstart,
+                                              const float* xweight, int Kx, float* out, int B, int H, int W, int mirror_too,
+                                              long mirror_offset, ocv_stream_t stream) {
+  const pixfmt::Planes pl{{plane0, plane1, plane2}, {frame_stride0, frame_stride1, frame_stride2}, {row_stride0, row_stride1, row_stride2}};
+  OCV_CHECK_ARG(table && out && ystart && yweight && xstart && xweight, "ocv_frame_resize_ingest_format: null pointer (table / out / tap tables)");
+  OCV_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1 && Hw >= 1 && Ww >= 1,
+                "ocv_frame_resize_ingest_format: bad sizes (B, H, W, Hs, Ws, Hw, Ww must be >= 1, B <= 65535)");
+  if (pixfmt::check_source("ocv_frame_resize_ingest_format", format, pl, yuv_table, B, Hs, Ws)) return -1;
+  OCV_CHECK_ARG(top >= 0 && left >= 0 && (long)top + Hw <= Hs && (long)left + Ww <= Ws,
+                "ocv_frame_resize_ingest_format: window outside the frame");
+  OCV_CHECK_ARG(ratio_ok(Hw, Ww, H, W),
+                "ocv_frame_resize_ingest_format: window %d x %d -> %d x %d shrinks by more than OCV_FRAME_RESIZE_MAX_RATIO = %d along an axis "
+                "(the filter is not truncated: resize in two steps)", Hw, Ww, H, W, OCV_FRAME_RESIZE_MAX_RATIO);
+  OCV_CHECK_ARG(Ky >= 1 && Kx >= 1 && Ky <= OCV_FRAME_RESIZE_MAX_TAPS && Kx <= OCV_FRAME_RESIZE_MAX_TAPS,
+                "ocv_frame_resize_ingest_format: %d / %d taps per row; 1 .. OCV_FRAME_RESIZE_MAX_TAPS = %d are taken", Ky, Kx,
+                OCV_FRAME_RESIZE_MAX_TAPS);
+  OCV_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(ystart) |
+                  reinterpret_cast<uintptr_t>(yweight) | reinterpret_cast<uintptr_t>(xstart) | reinterpret_cast<uintptr_t>(xweight)) & 3) == 0,
+                "ocv_frame_resize_ingest_format: out / table / tap tables must be 4-byte aligned");
+  OCV_CHECK_ARG(!mirror_too || mirror_offset >= (long)B * 3 * H * W || mirror_offset <= -(long)B * 3 * H * W,
+                "ocv_frame_resize_ingest_format: the mirrored half overlaps the batch (mirror_offset is in elements, |offset| >= B * 3 * H * W)");
+  Plan p;
+  OCV_CHECK_ARG(plan_tile(Hw, Ww, H, W, Ky, Kx, &p, pixfmt::is_yuv(format) ? pixfmt::YUV_TABLE_WORDS : 0),
+                "ocv_frame_resize_ingest_format: no tile fits %d bytes of LDS", FRAME_RESIZE_LDS_MAX);
+  const ResizeCall c{table, ystart, yweight, xstart, xweight, out, mirror_offset, top, left, Hw, Ww, H, W, Ky, Kx};
+  const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (!mirror_too || (mirror_offset & 3) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((W + (1 << p.tw_shift) - 1) >> p.tw_shift, (H + (1 << p.th_shift) - 1) >> p.th_shift, B);
+  OCV_CHECK_ARG(grid.y <= 65535, "ocv_frame_resize_ingest_format: H = %d is more than 65535 tiles tall", H);
+  switch (format) {
+    case OCV_PIXFMT_RGB24: launch_resize<OCV_PIXFMT_RGB24>(pl, yuv_table, c, p, vec, mirror_too != 0, grid, st); break;
+    case OCV_PIXFMT_BGR24: launch_resize<OCV_PIXFMT_BGR24>(pl, yuv_table, c, p, vec, mirror_too != 0, grid, st); break;
+    case OCV_PIXFMT_RGBA32: launch_resize<OCV_PIXFMT_RGBA32>(pl, yuv_table, c, p, vec, mirror_too != 0, grid, st); break;
+    case OCV_PIXFMT_BGRA32: launch_resize<OCV_PIXFMT_BGRA32>(pl, yuv_table, c, p, vec, mirror_too != 0, grid, st); break;
+    case OCV_PIXFMT_NV12: launch_resize<OCV_PIXFMT_NV12>(pl, yuv_table, c, p, vec, mirror_too != 0, grid, st); break;
+    default: launch_resize<OCV_PIXFMT_I420>(pl, yuv_table, c, p, vec, mirror_too != 0, grid, st); break;
+  }
+  OCV_CHECK_LAUNCH("ocv_frame_resize_ingest_format");
   return 0;
 }

@@ -13,6 +13,7 @@ import torch
 
 from .. import _lib
 from .._lib import check
+from ..pixel_formats import PixelFormat, PlanarFrames, plane_strides
 from ._core import _ptr, _req, _stream, timed
 
 
@@ -191,6 +192,170 @@ def frame_resize_ingest(frames_u8: torch.Tensor, table: torch.Tensor, size: Tupl
                                           ys.data_ptr(), yw.data_ptr(), int(yw.shape[1]), xs.data_ptr(), xw.data_ptr(), int(xw.shape[1]),
                                           out.data_ptr() + 4 * plane * int(out_index), B, H, W, 1 if mirror_too else 0, half * plane,
                                           _stream()), "ocv_frame_resize_ingest")
+    return out
+
+
+_YUV = {}                         # (device type, index, matrix, range) -> the device copy of ``pixel_formats.yuv_tables``
+
+
+def frame_yuv_tables(device, pixel_format) -> Optional[torch.Tensor]:
+    """The int32 [5, 256] tables of Statement P of a 4:2:0 ``pixel_format`` on ``device`` (``pixel_formats.yuv_tables``), uploaded on
+    the current stream when first used there and kept; None for a packed format."""
+    fmt = PixelFormat.of(pixel_format)
+    if not fmt.planar:
+        return None
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.HipLibraryError(f"frame_yuv_tables: {device} is no ROCm GPU (there is no CPU fallback)")
+    index = torch.cuda.current_device() if device.index is None else device.index
+    key = (device.type, index, fmt.matrix, fmt.range)
+    t = _YUV.get(key)
+    if t is None:
+        t = _YUV[key] = fmt.tables().to(device)
+    return t
+
+
+def _yuv_on(device, fmt: PixelFormat, given: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if not fmt.planar:
+        return None
+    if given is None:
+        return frame_yuv_tables(device, fmt)
+    _req(given, "yuv_tables", torch.int32)
+    if tuple(given.shape) != (5, 256):
+        raise ValueError(f"yuv_tables must be int32 [5, 256], got {tuple(given.shape)}")
+    return given
+
+
+def _source(frames, fmt: PixelFormat, who: str):
+    """(B, Hs, Ws, device, the nine plane arguments of a ``*_format`` entry point) of a frame batch in ``fmt``: a ``PlanarFrames`` for the
+    4:2:0 formats, a uint8 tensor [B, Hs, Ws, 3 | 4] (rows / frames may be strided) for the packed ones."""
+    if fmt.planar:
+        if not isinstance(frames, PlanarFrames) or frames.name != fmt.name:
+            raise TypeError(f"{who}: {fmt.name} frames are a PlanarFrames({fmt.name!r}, ...), got "
+                            f"{frames if isinstance(frames, PlanarFrames) else type(frames).__name__}")
+        args = []
+        for i, p in enumerate(frames.planes):
+            _req(p, f"{who}: plane {i}", torch.uint8, contiguous=False)
+            args += [p.data_ptr(), *plane_strides(p)]
+        args += [None, 0, 0] * (3 - len(frames.planes))
+        B, Hs, Ws = frames.shape
+        return B, Hs, Ws, frames.device, args
+    ch = fmt.channels
+    _req(frames, f"{who}: frames", torch.uint8, contiguous=False)
+    if frames.dim() != 4 or frames.shape[3] != ch:
+        raise ValueError(f"{who}: {fmt.name} frames are [B, Hs, Ws, {ch}], got {tuple(frames.shape)}")
+    B, Hs, Ws = (int(s) for s in frames.shape[:3])
+    if B < 1 or Hs < 1 or Ws < 1:
+        raise ValueError(f"{who}: empty frames {tuple(frames.shape)}")
+    st = frames.stride()
+    if st[3] != 1 or st[2] != ch:
+        raise ValueError(f"{who}: the pixels of a row must be dense (strides {st})")
+    row = int(st[1]) if Hs > 1 else Ws * ch
+    frame = int(st[0]) if B > 1 else Hs * row
+    if row < Ws * ch or frame < (Hs - 1) * row + Ws * ch:
+        raise ValueError(f"{who}: overlapping rows / frames (strides {st})")
+    return B, Hs, Ws, frames.device, [frames.data_ptr(), frame, row, None, 0, 0, None, 0, 0]
+
+
+def _ingest_out(out, out_index: int, B: int, H: int, W: int, mirror_too: bool, device, who: str):
+    """The ``out`` / ``out_index`` rules of ``frame_ingest`` -> (out, out_index, images per half)."""
+    if out is None:
+        out = torch.empty((2 * B if mirror_too else B, 3, H, W), dtype=torch.float32, device=device)
+        out_index = 0
+    else:
+        _req(out, f"{who}: out")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (3, H, W):
+            raise ValueError(f"{who}: out must be [N, 3, {H}, {W}], got {tuple(out.shape)}")
+    N = int(out.shape[0])
+    half = N // 2 if mirror_too else N
+    if (mirror_too and N % 2) or out_index < 0 or out_index + B > half:
+        raise ValueError(f"{who}: {B} image(s) at index {out_index} do not fit out {tuple(out.shape)}"
+                         f"{' (first half: the second takes the mirrors)' if mirror_too else ''}")
+    return out, int(out_index), half
+
+
+def frame_ingest_format(frames, table: torch.Tensor, pixel_format, top: int = 0, left: int = 0, size: Optional[Tuple[int, int]] = None,
+                        mirror_too: bool = False, out: Optional[torch.Tensor] = None, out_index: int = 0,
+                        yuv_tables: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``frame_ingest`` for frames of any ``pixel_format`` (a ``PixelFormat`` or a name): a uint8 tensor [B, Hs, Ws, 3 | 4] for the
+    packed formats, a ``PlanarFrames`` for nv12 / i420, whose pixels become R, G, B bytes by Statement P (``pixel_formats``) inside the
+    launch.  Every other argument as ``frame_ingest`` takes it; bit-equal to ``frame_ingest`` on the converted frames.  One launch
+    (ocv_frame_ingest_format) on the current stream; a 4:2:0 format's tables are uploaded on it when first used
+    (``frame_yuv_tables``), or passed as ``yuv_tables`` (the int32 [5, 256] device tensor of the format's matrix and range)."""
+    lib = _lib.load()
+    fmt = PixelFormat.of(pixel_format)
+    B, Hs, Ws, device, planes = _source(frames, fmt, "frame_ingest_format")
+    _req(table, "table")
+    if tuple(table.shape) != (3, 256):
+        raise ValueError(f"frame_ingest_format: table must be [3, 256], got {tuple(table.shape)}")
+    H, W = _window(Hs, Ws, int(top), int(left), size, "frame_ingest_format")
+    out, out_index, half = _ingest_out(out, out_index, B, H, W, mirror_too, device, "frame_ingest_format")
+    yuv = _yuv_on(device, fmt, yuv_tables)
+    plane = 3 * H * W
+    with timed("frame_ingest_format"):
+        check(lib.ocv_frame_ingest_format(fmt.id, *planes, _ptr(yuv), Hs, Ws, int(top), int(left), table.data_ptr(),
+                                          out.data_ptr() + 4 * plane * out_index, B, H, W, 1 if mirror_too else 0, half * plane,
+                                          _stream()), "ocv_frame_ingest_format")
+    return out
+
+
+def frame_resize_ingest_format(frames, table: torch.Tensor, size: Tuple[int, int], pixel_format, top: int = 0, left: int = 0,
+                               window: Optional[Tuple[int, int]] = None, mirror_too: bool = False, out: Optional[torch.Tensor] = None,
+                               out_index: int = 0, taps: Optional[Sequence[torch.Tensor]] = None,
+                               yuv_tables: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``frame_resize_ingest`` for frames of any ``pixel_format`` (as ``frame_ingest_format`` takes them): the conversion happens
+    while the window's pixels are staged, the two tap passes are ``frame_resize_ingest``'s -- bit-equal to it on the converted frames.
+    One launch (ocv_frame_resize_ingest_format) on the current stream."""
+    lib = _lib.load()
+    fmt = PixelFormat.of(pixel_format)
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError(f"frame_resize_ingest_format: bad output size {tuple(size)}")
+    B, Hs, Ws, device, planes = _source(frames, fmt, "frame_resize_ingest_format")
+    Hw, Ww = _window(Hs, Ws, int(top), int(left), window, "frame_resize_ingest_format")
+    if not frame_resize_supported(Hw, Ww, H, W):
+        raise ValueError(f"frame_resize_ingest_format: a {Hw} x {Ww} window to {H} x {W} shrinks by more than {FRAME_RESIZE_MAX_RATIO} "
+                         "along an axis, the most one launch takes (the filter is never truncated): resize in two steps")
+    _req(table, "table")
+    if tuple(table.shape) != (3, 256):
+        raise ValueError(f"frame_resize_ingest_format: table must be [3, 256], got {tuple(table.shape)}")
+    if taps is None:
+        taps = frame_resize_taps(device, Hw, Ww, H, W)
+    if len(taps) != 4:
+        raise ValueError("frame_resize_ingest_format: taps = (ystart, yweight, xstart, xweight)")
+    ys, yw, xs, xw = taps
+    for name, st, wt, n in (("y", ys, yw, H), ("x", xs, xw, W)):
+        _req(st, f"taps: {name}start", torch.int32)
+        _req(wt, f"taps: {name}weight")
+        if tuple(st.shape) != (n,) or wt.dim() != 2 or wt.shape[0] != n or wt.shape[1] < 1:
+            raise ValueError(f"frame_resize_ingest_format: taps of the {name} axis must be int32 [{n}] and fp32 [{n}, K], got "
+                             f"{tuple(st.shape)} / {tuple(wt.shape)}")
+    out, out_index, half = _ingest_out(out, out_index, B, H, W, mirror_too, device, "frame_resize_ingest_format")
+    yuv = _yuv_on(device, fmt, yuv_tables)
+    plane = 3 * H * W
+    with timed("frame_resize_ingest_format"):
+        check(lib.ocv_frame_resize_ingest_format(fmt.id, *planes, _ptr(yuv), Hs, Ws, int(top), int(left), Hw, Ww, table.data_ptr(),
+                                                 ys.data_ptr(), yw.data_ptr(), int(yw.shape[1]), xs.data_ptr(), xw.data_ptr(),
+                                                 int(xw.shape[1]), out.data_ptr() + 4 * plane * out_index, B, H, W,
+                                                 1 if mirror_too else 0, half * plane, _stream()), "ocv_frame_resize_ingest_format")
+    return out
+
+
+def frames_to_rgb24(frames, pixel_format, top: int = 0, left: int = 0, size: Optional[Tuple[int, int]] = None,
+                    out: Optional[torch.Tensor] = None, yuv_tables: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ``size`` = (Hw, Ww) window at (top, left) (default: the rest of the frame) of frames of any ``pixel_format`` (as
+    ``frame_ingest_format`` takes them) -> packed RGB uint8 [B, Hw, Ww, 3]: Statement P for the 4:2:0 formats, the bytes re-ordered for
+    the packed ones.  ``out``: a contiguous uint8 [B, Hw, Ww, 3] to write.  One launch (ocv_frames_to_rgb24) on the current stream,
+    every output byte written."""
+    lib = _lib.load()
+    fmt = PixelFormat.of(pixel_format)
+    B, Hs, Ws, device, planes = _source(frames, fmt, "frames_to_rgb24")
+    Hw, Ww = _window(Hs, Ws, int(top), int(left), size, "frames_to_rgb24")
+    out = _out_slice(out, (B, Hw, Ww, 3), torch.uint8, device, "frames_to_rgb24")
+    yuv = _yuv_on(device, fmt, yuv_tables)
+    with timed("frames_to_rgb24"):
+        check(lib.ocv_frames_to_rgb24(fmt.id, *planes, _ptr(yuv), Hs, Ws, int(top), int(left), out.data_ptr(), B, Hw, Ww, _stream()),
+              "ocv_frames_to_rgb24")
     return out
 
 
@@ -500,7 +665,7 @@ def depth_unproject(depth: torch.Tensor, K: torch.Tensor, capacity: int, stride:
     return res
 
 
-__all__ = ["frame_ingest", "resize_taps", "frame_resize_supported", "frame_resize_taps", "frame_resize_ingest", "FRAME_RESIZE_MAX_RATIO",
+__all__ = ["frame_ingest", "frame_ingest_format", "frame_resize_ingest_format", "frames_to_rgb24", "frame_yuv_tables", "resize_taps", "frame_resize_supported", "frame_resize_taps", "frame_resize_ingest", "FRAME_RESIZE_MAX_RATIO",
            "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics",
            "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
            "unproject_grid", "UNPROJECT_TILE"]

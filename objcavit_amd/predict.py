@@ -22,6 +22,7 @@ from . import hip_ops
 from ._lib import HipLibraryError
 from .object_depth import DEFAULT_QUANTILES, ObjectDepths, object_depths, pad_boxes
 from .object_metrics import ObjectMetrics, object_metrics as _object_metrics
+from .pixel_formats import PixelFormat, PlanarFrames
 from .point_cloud import PointCloud
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
@@ -60,7 +61,7 @@ class _ObjectsResult(PredictResult):
 # boxes and, for the point cloud, its intrinsics (of the source frames, on the device)
 _Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics", "size"], defaults=(None, None))     # size: the step's final size (``resize``)
 
-Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
+Frames = Union[torch.Tensor, PlanarFrames, Sequence[Union[torch.Tensor, PlanarFrames]]]
 
 
 def _dataset(args):
@@ -229,12 +230,40 @@ def _frame_list(frames: Frames, what: str, dims: int) -> List[torch.Tensor]:
     return out
 
 
+def _frames_of(frames: Frames, what: str, fmt: Optional[PixelFormat]) -> list:
+    """``_frame_list`` for the ``pixel_format`` keyword: without it (None) today's packed RGB frames; a packed format takes tensors
+    [B, Hs, Ws, 3 | 4] (or a list of single frames [Hs, Ws, 3 | 4]); a 4:2:0 format takes a ``PlanarFrames`` or a list of them (each a
+    frame, or a batch, of its own size)."""
+    if fmt is None:
+        return _frame_list(frames, what, 4)
+    if not fmt.planar:
+        out = _frame_list(frames, what, 4)
+        for f in out:
+            if int(f.shape[3]) != fmt.channels:
+                raise ValueError(f"{what}: {fmt.name} frames have {fmt.channels} bytes per pixel, got {tuple(f.shape)}")
+        return out
+    out = [frames] if isinstance(frames, PlanarFrames) else list(frames)
+    if not out:
+        raise ValueError(f"{what}: empty list")
+    for f in out:
+        if not isinstance(f, PlanarFrames) or f.name != fmt.name:
+            raise ValueError(f"{what}: {fmt.name} frames are a PlanarFrames({fmt.name!r}, ...) or a list of them, got "
+                             f"{f if isinstance(f, PlanarFrames) else type(f).__name__}")
+    return out
+
+
+def _tensors_of(frames: list) -> List[torch.Tensor]:
+    """Every tensor a list of frame batches is made of: the frames themselves, or the planes of ``PlanarFrames``."""
+    return [t for f in frames for t in (f.planes if isinstance(f, PlanarFrames) else (f,))]
+
+
 class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
     def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None,
-                 object_metrics=None, resize=None):
+                 object_metrics=None, resize=None, pixel_format=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
+        self.fmt = None if pixel_format is None else PixelFormat.of(pixel_format)      # None: rgb24 through the rgb24 calls
         self.resize = _model_size(resize)
         self.readout = _readout_options(object_depth)
         self.errors = _metric_options(object_metrics)
@@ -280,9 +309,22 @@ class _Ends:
                              f"{hip_ops.FRAME_RESIZE_MAX_RATIO} along an axis (hip_ops.frame_resize_ingest)")
         return hip_ops.frame_resize_taps(frames[0].device, Hw, Ww, *self.resize)
 
-    def ingest(self, frames: List[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def frames_of(self, frames: Frames, what: str) -> list:
+        return _frames_of(frames, what, self.fmt)
+
+    def yuv_of(self, frames: list) -> Optional[torch.Tensor]:
+        """With a 4:2:0 ``pixel_format``: the device tables of Statement P, uploaded on the current stream when first used on that
+        device and kept (``hip_ops.frame_yuv_tables``); None otherwise."""
+        if self.fmt is None or not self.fmt.planar:
+            return None
+        if frames[0].device.type != "cuda":
+            raise HipLibraryError(f"frames are on {frames[0].device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
+        return hip_ops.frame_yuv_tables(frames[0].device, self.fmt)
+
+    def ingest(self, frames: list, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``.  With ``resize``
-        every frame's window is resized to the model's size by that launch (``hip_ops.frame_resize_ingest``)."""
+        every frame's window is resized to the model's size by that launch (``hip_ops.frame_resize_ingest``); with ``pixel_format``
+        the frames are read in that format by the same launch (``hip_ops.frame_ingest_format`` / ``frame_resize_ingest_format``)."""
         for f in frames:
             if f.device.type != "cuda":
                 raise HipLibraryError(f"frames are on {f.device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
@@ -298,7 +340,13 @@ class _Ends:
         i = 0
         for f in frames:
             top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            if taps is None:
+            if self.fmt is not None:
+                if taps is None:
+                    hip_ops.frame_ingest_format(f, table, self.fmt, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
+                else:
+                    hip_ops.frame_resize_ingest_format(f, table, (H, W), self.fmt, top, left, (Hw, Ww), mirror_too=self.flip_tta, out=out,
+                                                       out_index=i, taps=taps)
+            elif taps is None:
                 hip_ops.frame_ingest(f, table, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
             else:
                 hip_ops.frame_resize_ingest(f, table, (H, W), top, left, (Hw, Ww), mirror_too=self.flip_tta, out=out, out_index=i, taps=taps)
@@ -356,7 +404,9 @@ class _Ends:
     def points_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor]) -> PointCloud:
         """The point cloud of a step's final map: one launch pair per entry of ``frames`` (a list of differently sized frames has an
         origin -- hence a principal point -- and a colour source per frame) into one set of buffers.  K is shifted by each frame's
-        window origin (``point_cloud.shift_intrinsics``'s statement, the offsets cached on the device)."""
+        window origin (``point_cloud.shift_intrinsics``'s statement, the offsets cached on the device).  With a ``pixel_format`` other
+        than rgb24 the colour is read from the window's RGB24 copy, made by one more launch in front (``hip_ops.frames_to_rgb24``):
+        bytes 12 - 14 of a record are Statement P's R, G, B."""
         c, depth = self.cloud, maps["depth"]
         B, _, H, W = (int(v) for v in depth.shape)
         gh, gw = hip_ops.unproject_grid(H, W, c["stride"])
@@ -372,10 +422,13 @@ class _Ends:
         for f in frames:
             n = int(f.shape[0])
             top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
+            colour, ctop, cleft = (f if c["colour"] else None), top, left
+            if colour is not None and self.fmt is not None and self.fmt.name != "rgb24":
+                colour, ctop, cleft = hip_ops.frames_to_rgb24(f, self.fmt, top, left, (H, W)), 0, 0
             hip_ops.depth_unproject(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), cap, stride=c["stride"], near=c["near"],
                                     far=c["far"], confidence=None if conf is None else conf[i:i + n], min_confidence=c["min_confidence"],
                                     depth_std=None if std is None else std[i:i + n], max_std=c["max_std"],
-                                    frames=f if c["colour"] else None, top=top, left=left, want_pixel=c["pixel"], out=bufs, image_index=i)
+                                    frames=colour, top=ctop, left=cleft, want_pixel=c["pixel"], out=bufs, image_index=i)
             i += n
         return PointCloud(bufs["points"], bufs["counts"], bufs["total"], bufs.get("pixel"))
 
@@ -469,6 +522,12 @@ class Predictor:
     ``intrinsics=`` and the cloud's colour stay in window / source-frame pixels exactly as described here; only boxes fed to the MODEL's
     object provider live in model-input pixels (``boxes_to_model``).  A window may shrink by at most
     ``hip_ops.FRAME_RESIZE_MAX_RATIO`` along an axis.
+    ``pixel_format``: None (packed RGB, as above, through the same launches as ever), a ``PixelFormat`` or a name
+    (objcavit_amd/pixel_formats.py): "bgr24" (OpenCV), "rgba32" / "bgra32" (tensors [B, Hs, Ws, 4], alpha ignored), "nv12" (hardware
+    decoders) / "i420" (software decoders) -- the frames are then a ``PlanarFrames`` (or a list of them), and Y, Cb, Cr become R, G, B by
+    Statement P (integer, tables by the host for the format's ``matrix`` and ``range``; chroma replicated) INSIDE the ingest launch, with
+    or without ``resize``.  Everything behind the ingest is unchanged; the point cloud's colour is read from the window's RGB24 copy
+    (``hip_ops.frames_to_rgb24``, one more launch).
     ``object_depth``: None, or a dict with some of ``quantiles`` / ``shrink`` -- the per-object readout (objcavit_amd/object_depth.py).
     With it, ``boxes=`` of a call -- the boxes a detector found in the B frames, in pixels of the cropped window: a list of [N_i, >= 4]
     tensors / None, an (xywh, counts) pair or a ``PaddedObjects``; independent of the objects the model's provider is fed -- is read out
@@ -491,11 +550,12 @@ class Predictor:
     by keyword."""
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
-                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, crop: Optional[Tuple[int, int, int, int]] = None,
-                 resize: Optional[Tuple[int, int]] = None, object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None,
-                 object_depth: Optional[dict] = None):
+                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, pixel_format=None,
+                 crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
+                 object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
+                          pixel_format)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -513,7 +573,7 @@ class Predictor:
         want = _check_want(want)
         if _need_stats(want) or (intrinsics is not None and _cloud_want(self.ends.cloud)):
             _turn_stats_on(self.model)
-        frames = _frame_list(frames_u8, "frames_u8", 4)
+        frames = self.ends.frames_of(frames_u8, "frames_u8")
         B = sum(int(f.shape[0]) for f in frames)
         size = self.ends.window_of(frames)
         out, mirror = self._forward(frames, B)
@@ -536,6 +596,8 @@ class PipelinedPredictor(_SlotPipeline):
     stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
     graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
+    ``pixel_format``: as ``Predictor``'s; every plane of a submitted ``PlanarFrames`` is held like the frames, the tables of Statement P
+    are uploaded on the caller's stream when first used, a re-run step is ingested again from its kept planes.
 
         pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
         for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
@@ -547,17 +609,18 @@ class PipelinedPredictor(_SlotPipeline):
 
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
-                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None,
+                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize)
+        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
+                          pixel_format)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
-        ex = _frame_list(example_frames, "example_frames", 4)
+        ex = self.ends.frames_of(example_frames, "example_frames")
         self.B = sum(int(f.shape[0]) for f in ex)
         self.size = self.ends.window_of(ex)
         both = self.ends.ingest(ex)
@@ -589,14 +652,17 @@ class PipelinedPredictor(_SlotPipeline):
         the cloud's buffers are made per step on the slot's stream, its workspace is the slot's.
         ``object_features``: as ``PipelinedValidation.submit``'s -- a ``Detections`` of the B frames (the model's provider a
         ``DeviceObjectProvider``, with ``mirror_width`` under flip-TTA) is written into the slot's static buffers by one launch."""
-        frames = _frame_list(frames_u8, "frames_u8", 4)
+        frames = self.ends.frames_of(frames_u8, "frames_u8")
         size = self.ends.window_of(frames)
         if sum(int(f.shape[0]) for f in frames) != self.B or (size != self.size and self.ends.resize is None):
             raise ValueError(f"captured for {self.B} frame(s) cropped to {self.size}")
         # ``resize``: a window size seen for the first time has its tap tables uploaded HERE, on the caller's stream, which the slot's
         # stream waits for before its launch; the cache keeps them alive, and they are held like the frames
+        # ``pixel_format``: likewise the tables of Statement P; every plane of a ``PlanarFrames`` is held like the frames
         taps = self.ends.taps_of(frames)
-        held = list(taps or ()) + list(frames) + ([depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or []))
+        yuv = self.ends.yuv_of(frames)
+        held = list(taps or ()) + ([] if yuv is None else [yuv]) + _tensors_of(frames)
+        held += [depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or [])
         boxes = self.ends.boxes_on(boxes, frames[0].device, self.B)
         held += list(boxes or ())
         K = self.ends.intrinsics_on(intrinsics, frames[0].device, self.B)
