@@ -81,7 +81,7 @@ int ocv_attention_set_dispatch(int form);
 /* out[z][m][n] = act( sum_k A[z][m][k] * W(n,k) + bias[n] )
  * W(n,k) = W[z][n*ldw + k] if w_kn == 0 (nn.Linear layout, [N,K])
  *        = W[z][k*ldw + n] if w_kn != 0 ([K,N] layout).
- * batch strides (elements) may be 0 to share an operand across the batch.
+ * batch strides (elements) may be 0 to share an operand across the batch; 1 <= batch <= 65535 (the grid's z extent).
  * Replaces nn.Linear / nn.Sequential(Linear, LeakyReLU, ...) at
  * modules/ObjCAViT.py:257-282,289,299-303,324-330,378 and
  * modules/miniViT.py:16-20,33; also used for the in/out projections of
@@ -202,7 +202,11 @@ int ocv_encoder_layer_fwd(const float* x, const ocv_encoder_layer_params* p, con
  * layout, row stride ldw) is split and packed once per weight version by ocv_pack_split3_fwd into MFMA B-operand
  * fragments, ocv_split3_packed_elems(N, K) bf16 elements:
  *   packed[((jt * ceil(K/16) + s) * 3 + part) * 512 + lane * 8 + e] = part of W[32 jt + (lane & 31)][16 s + 8 (lane >> 5) + e]
- * (zero beyond N / K).  K a multiple of 8.  Same reference lines as ocv_linear_fwd /
+ * (zero beyond N / K).  K a multiple of 8.  The packers read W with scalar loads (any ldw >= K, any 4-byte aligned W); `packed`
+ * must be 16-byte aligned.  ocv_linear_split3_fwd and ocv_linear_residual_layernorm_split3_fwd stage the rows of A with
+ * 16-byte loads: A AND w_packed MUST BE 16-BYTE ALIGNED AND lda A MULTIPLE OF 4 (lda >= K; both return -1 otherwise -- unlike
+ * ocv_linear_fwd, which takes any base and leading dimension and falls back to scalar loads).  ldo / ldres / out / residual /
+ * bias: any 4-byte aligned address, ldo / ldres >= N.  Same reference lines as ocv_linear_fwd /
  * ocv_linear_residual_layernorm_fwd / ocv_ffn_residual_layernorm_fwd. */
 size_t ocv_split3_packed_elems(int N, int K);
 int ocv_pack_split3_fwd(const float* W, int ldw, int N, int K, void* packed, ocv_stream_t stream);

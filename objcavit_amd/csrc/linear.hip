@@ -517,6 +517,7 @@ extern "C" int ocv_linear_fwd(const float* A, int lda, long strideA, const float
                               int act, ocv_stream_t stream) {
   OCV_CHECK_ARG(A && W && out, "ocv_linear_fwd: null pointer");
   OCV_CHECK_ARG(batch >= 1 && M >= 0 && N >= 1 && K >= 1, "ocv_linear_fwd: bad sizes batch=%d M=%d N=%d K=%d", batch, M, N, K);
+  OCV_CHECK_ARG(batch <= 65535, "ocv_linear_fwd: grid too large (batch=%d: at most 65535)", batch);      // batch is gridDim.z
   OCV_CHECK_ARG(lda >= K && ldo >= N && ldw >= (w_kn ? N : K), "ocv_linear_fwd: leading dimension too small");
   OCV_CHECK_ARG(act >= 0 && act <= 2, "ocv_linear_fwd: unknown activation %d", act);
   if (M == 0) return 0;
