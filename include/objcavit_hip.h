@@ -42,7 +42,8 @@ typedef void* ocv_stream_t;
 #define OCV_ABI_VERSION 5 /* 5: round 6 ADDED ocv_attention_set_dispatch (the library reads no environment variable any more),
  * ocv_conv3x3_packed_taps_k / ocv_conv3x3_split_packed_taps_fwd; nothing removed or changed: a caller built against 4 keeps working;
  * later ADDED (still 5: a new symbol changes nothing for an existing caller) ocv_conv3x3_nhwc_strided_fwd (EfficientNetV2),
- * ocv_depth_metrics_loss_workspace_bytes / ocv_depth_metrics_loss_fwd (validation loss);
+ * ocv_depth_metrics_loss_workspace_bytes / ocv_depth_metrics_loss_fwd (validation loss),
+ * ocv_depth_normals_fwd / ocv_normals_gather_fwd (surface normals of the final map, Statement N);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -838,6 +839,42 @@ int ocv_depth_unproject_fwd(const float* depth, const float* K, const float* con
                             long frame_stride, long row_stride, int Hs, int Ws, int top, int left, int B, int H, int W, int sy, int sx,
                             float near, float far, float min_confidence, float max_std, int cap, float* points, int* pixel, int* counts,
                             int* total, void* workspace, size_t workspace_bytes, ocv_stream_t stream);
+/* Surface normals of the final map, STATEMENT N (no counterpart in the reference; the statement the tests compare against is
+ * tests/normals_ref.py).  The final map is a bilinear enlargement of the head's map, hence piecewise bilinear: one-pixel differences give
+ * faceted normals, so the slope is the LEAST-SQUARES plane slope over a (2r + 1)^2 window.
+ * depth [B][1][H][W] fp32 (the map of ocv_depth_finalize_fwd); K [B][4] fp32 in DEVICE memory = fx, fy, cx, cy in pixels of the map's own
+ * grid, the integer index (x, y) being the pixel's centre (as ocv_depth_unproject_fwd takes it); radius r in 1..4; near <= far;
+ * edge_ratio > 0.
+ * VALIDITY (bit-exact: every operation fp32, rounded on its own).  Pixel (x, y) of image b is VALID iff
+ *   the window [x - r, x + r] x [y - r, y + r] lies inside the map;
+ *   every z of the window is finite (no NaN, no +-inf) and near <= z <= far;
+ *   with zc = z(x, y), t = edge_ratio * zc, wmax / wmin the window's extremes:  wmax - zc <= t  and  zc - wmin <= t  (no depth
+ *     discontinuity inside the window);
+ *   fx, fy are finite and > 0 and cx, cy finite (else the image has no valid pixel).
+ * SLOPES, with D = (2r + 1) * 2 * sum_{i=1..r} i^2 (the reference: fp64 from the fp32 map; the kernel: fp32, sums in its own order):
+ *   zu = sum_{j=-r..r} sum_{i=1..r} i * (z(x + i, y + j) - z(x - i, y + j)) / D
+ *   zv = sum_{i=-r..r} sum_{j=1..r} j * (z(x + i, y + j) - z(x + i, y - j)) / D
+ * NORMAL of the back-projected surface P = ((x - cx) z / fx, (y - cy) z / fy, z), pointing at the camera (n . P = -z^2 / |m| < 0):
+ *   m = ( fx * zu,  fy * zv,  -(zc + (x - cx) * zu + (y - cy) * zv) ),   n = m / |m|   (m = 0, a flat window at z = 0: n = (0, 0, -1))
+ * OUTPUTS, each nullable, at least one given, EVERY element of a given output written:
+ *   normals      fp32  [B][3][H][W]  n at valid pixels, (0, 0, 0) at invalid ones
+ *   normals_rgb8 uint8 [B][H][W][3]  rint(127.5 * n + 127.5) clamped to 0..255 per component; (0, 0, 0) at invalid pixels
+ *   valid        uint8 [B][H][W]     1 / 0
+ * One launch, one 256-thread workgroup per 64 x 16 tile: the tile and its halo of r staged once into LDS, a pass per row (ramp sum, box
+ * sum, min, max of the 2r + 1 horizontal neighbours), a pass per pixel (their vertical combination, predicate, normalisation, stores).
+ * No atomics, no workspace, no allocation, no synchronisation, nothing read on the host (capturable); two calls give identical bytes.
+ * Images are independent: a batch can be filled by one call per image with offset pointers.
+ * -1 with a message before the launch on: a null depth / K, all outputs null, r outside 1..4, non-positive sizes, H * W or B * tiles
+ * at or above 2^31, near > far (or NaN), edge_ratio <= 0 (or NaN), K not 16-byte aligned, depth / normals not 4-byte aligned. */
+int ocv_depth_normals_fwd(const float* depth, const float* K, int H, int W, int r, float near, float far, float edge_ratio, float* normals,
+                          uint8_t* normals_rgb8, uint8_t* valid, int B, ocv_stream_t stream);
+/* A normal for every point of ocv_depth_unproject_fwd's cloud: normals [B][3][H][W] (above), pixel int32 [B][cap] and counts int32 [B] (the
+ * cloud's; counts is read on the device only) -> out fp32 [B][cap][4], 16-byte aligned:  out[b][i] = (nx, ny, nz, 0) of pixel
+ * pixel[b][i] = y * W + x, ONE 16-byte store, for i < min(counts[b], cap); an index outside [0, H * W) gives (0, 0, 0, 0).  Rows at or
+ * beyond counts[b] are NOT WRITTEN (the cloud's rule).  One launch, no workspace, no atomics; capturable; bit-equal on repeat.
+ * -1 with a message before the launch on: a null pointer, non-positive sizes, H * W or B * cap at or above 2^31, a misaligned pointer. */
+int ocv_normals_gather_fwd(const float* normals, const int* pixel, const int* counts, int H, int W, int cap, float* out, int B,
+                           ocv_stream_t stream);
 /* Depth ERROR per detection box, and over objects against background: the validation metrics of ocv_depth_metrics_fwd, segmented by the
  * boxes of ocv_object_depth_fwd (no counterpart in the reference; the statement the tests compare against is tests/object_metrics_ref.py).
  * pred, pred_mirror (nullable, still mirrored), h, w, gt, H, W, min_depth, max_depth and the crop box: exactly as ocv_depth_metrics_fwd

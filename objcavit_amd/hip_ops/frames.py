@@ -1,7 +1,7 @@
 """hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip; a window of any size
 resized to the model's on the way in: csrc/frame_resize.hip), full-resolution depth
 maps out (csrc/depth_finalize.hip), and what is read out of the final map behind them: per-box statistics (csrc/object_depth.hip), the
-point cloud (csrc/point_cloud.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
+point cloud (csrc/point_cloud.hip), the surface normals (csrc/surface_normals.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
 static input)."""
 from __future__ import annotations
@@ -665,7 +665,86 @@ def depth_unproject(depth: torch.Tensor, K: torch.Tensor, capacity: int, stride:
     return res
 
 
+NORMALS_WANT = ("normals", "rgb8", "valid")
+NORMALS_MAX_RADIUS = 4            # include/objcavit_hip.h, Statement N: the window is (2r + 1)^2, r in 1..4
+
+
+def depth_normals(depth: torch.Tensor, K: torch.Tensor, radius: int = 2, near: float = 0.0, far: float = float("inf"),
+                  edge_ratio: float = 0.05, want: Tuple[str, ...] = ("normals",), out: Optional[dict] = None, image_index: int = 0) -> dict:
+    """Surface normals of the final map (Statement N of include/objcavit_hip.h): ``depth`` fp32 [B, 1, H, W], ``K`` fp32 [B, 4] on the
+    device = fx, fy, cx, cy in pixels of the map's grid (index (x, y) is the pixel's centre) -> {"normals": fp32 [B, 3, H, W], "rgb8":
+    uint8 [B, H, W, 3] = rint(127.5 n + 127.5), "valid": uint8 [B, H, W]}, those that ``want`` names.  A pixel is valid iff its
+    (2 radius + 1)^2 window lies inside the map, every depth in it is finite with near <= z <= far, the window's largest and smallest
+    depth are within ``edge_ratio`` * z of the centre's z (no depth discontinuity), and the image's fx, fy are finite and > 0, cx, cy
+    finite.  There the normal is m / |m|, m = (fx zu, fy zv, -(z + (x - cx) zu + (y - cy) zv)) with zu, zv the least-squares plane
+    slopes of the window: the unit normal of the back-projected surface, pointing at the camera.  Invalid pixels are all zero in every
+    output; every element is written.  ``out``: {name: tensor} of caller-owned buffers [N, ...] with N >= image_index + B; the B images
+    are written at ``image_index`` and the dict returned holds the whole buffers.  One launch (ocv_depth_normals_fwd) on the current
+    stream, nothing read on the host: capturable with ``out``."""
+    lib = _lib.load()
+    _req(depth, "depth")
+    if depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError(f"depth_normals: expected depth [B, 1, H, W], got {tuple(depth.shape)}")
+    B, _, H, W = (int(s) for s in depth.shape)
+    _req(K, "K")
+    if tuple(K.shape) != (B, 4):
+        raise ValueError(f"depth_normals: K must be fp32 [{B}, 4] = fx, fy, cx, cy, got {tuple(K.shape)}")
+    r = int(radius)
+    if not 1 <= r <= NORMALS_MAX_RADIUS or r != radius:
+        raise ValueError(f"depth_normals: radius must be an integer in 1..{NORMALS_MAX_RADIUS}, got {radius}")
+    if not float(near) <= float(far):
+        raise ValueError(f"depth_normals: near = {near} must be <= far = {far}")
+    if not C.c_float(float(edge_ratio)).value > 0.0:
+        raise ValueError(f"depth_normals: edge_ratio must be > 0, got {edge_ratio}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(NORMALS_WANT):
+        raise ValueError(f"depth_normals: want must name some of {NORMALS_WANT} (got {want})")
+    out = dict(out or {})
+    shapes = {"normals": (3, H, W), "rgb8": (H, W, 3), "valid": (H, W)}
+    N, index = B, int(image_index)
+    if out:
+        missing = [n for n in want if n not in out]
+        if missing:
+            raise ValueError(f"depth_normals: out has no {missing} (it needs {want})")
+        N = int(out[want[0]].shape[0]) if out[want[0]].dim() else 0
+        if index < 0 or index + B > N:
+            raise ValueError(f"depth_normals: {B} image(s) at index {index} do not fit buffers of {N}")
+    else:
+        index = 0
+    res = {n: _out_slice(out.get(n), (N,) + shapes[n], torch.float32 if n == "normals" else torch.uint8, depth.device, "depth_normals")
+           for n in NORMALS_WANT if n in want}
+    at = {n: t.data_ptr() + index * H * W * (12 if n == "normals" else 3 if n == "rgb8" else 1) for n, t in res.items()}
+    with timed("depth_normals"):
+        check(lib.ocv_depth_normals_fwd(depth.data_ptr(), K.data_ptr(), H, W, r, float(near), float(far), float(edge_ratio),
+                                        at.get("normals"), at.get("rgb8"), at.get("valid"), B, _stream()), "ocv_depth_normals_fwd")
+    return res
+
+
+def normals_gather(normals: torch.Tensor, pixel: torch.Tensor, counts: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A normal for every point of a cloud: ``normals`` fp32 [B, 3, H, W] (``depth_normals``), ``pixel`` int32 [B, cap] and ``counts``
+    int32 [B] (``depth_unproject(..., want_pixel=True)``, on the device) -> fp32 [B, cap, 4]: row i of image b = (nx, ny, nz, 0) of the
+    pixel ``pixel[b, i]`` = y * W + x, for i < counts[b].  ROWS AT OR BEYOND counts[b] ARE NOT WRITTEN (the cloud's rule).  One launch
+    (ocv_normals_gather_fwd), the counts are read on the device only."""
+    lib = _lib.load()
+    _req(normals, "normals")
+    if normals.dim() != 4 or normals.shape[1] != 3:
+        raise ValueError(f"normals_gather: expected normals [B, 3, H, W], got {tuple(normals.shape)}")
+    B, _, H, W = (int(s) for s in normals.shape)
+    _req(pixel, "pixel", torch.int32)
+    if pixel.dim() != 2 or int(pixel.shape[0]) != B or int(pixel.shape[1]) < 1:
+        raise ValueError(f"normals_gather: pixel must be int32 [{B}, cap >= 1], got {tuple(pixel.shape)}")
+    cap = int(pixel.shape[1])
+    _req(counts, "counts", torch.int32)
+    if tuple(counts.shape) != (B,):
+        raise ValueError(f"normals_gather: counts must be int32 [{B}], got {tuple(counts.shape)}")
+    out = _out_slice(out, (B, cap, 4), torch.float32, normals.device, "normals_gather")
+    with timed("normals_gather"):
+        check(lib.ocv_normals_gather_fwd(normals.data_ptr(), pixel.data_ptr(), counts.data_ptr(), H, W, cap, out.data_ptr(), B, _stream()),
+              "ocv_normals_gather_fwd")
+    return out
+
+
 __all__ = ["frame_ingest", "frame_ingest_format", "frame_resize_ingest_format", "frames_to_rgb24", "frame_yuv_tables", "resize_taps", "frame_resize_supported", "frame_resize_taps", "frame_resize_ingest", "FRAME_RESIZE_MAX_RATIO",
            "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics",
            "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
-           "unproject_grid", "UNPROJECT_TILE"]
+           "unproject_grid", "UNPROJECT_TILE", "depth_normals", "normals_gather", "NORMALS_WANT", "NORMALS_MAX_RADIUS"]

@@ -24,6 +24,7 @@ from .object_depth import DEFAULT_QUANTILES, ObjectDepths, object_depths, pad_bo
 from .object_metrics import ObjectMetrics, object_metrics as _object_metrics
 from .pixel_formats import PixelFormat, PlanarFrames
 from .point_cloud import PointCloud
+from .surface_normals import DEFAULT_EDGE_RATIO, DEFAULT_RADIUS, SurfaceNormals
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
@@ -38,23 +39,25 @@ PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "reco
 PredictResult.objects = None                   # the per-object readout (an ``ObjectDepths``) or None: an ATTRIBUTE, not a field
 PredictResult.points = None                    # the point cloud (a ``PointCloud``) or None: an attribute as well
 PredictResult.object_metrics = None            # the depth error per box / region (an ``ObjectMetrics``) or None: an attribute as well
+PredictResult.normals = None                   # the surface normals (a ``SurfaceNormals``) or None: an attribute as well
 
 
 class _ObjectsResult(PredictResult):
-    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` / ``object_metrics`` attributes hold the step's
-    ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics``."""
+    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` / ``object_metrics`` / ``normals`` attributes hold
+    the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals``."""
 
     def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, points: Optional[PointCloud] = None,
-                object_metrics: Optional[ObjectMetrics] = None, **kw):
+                object_metrics: Optional[ObjectMetrics] = None, normals: Optional[SurfaceNormals] = None, **kw):
         self = super().__new__(cls, *fields, **kw)
         self.objects = objects
         self.points = points
         self.object_metrics = object_metrics
+        self.normals = normals
         return self
 
     def _replace(self, **kw):
         return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects, points=self.points,
-                              object_metrics=self.object_metrics)
+                              object_metrics=self.object_metrics, normals=self.normals)
 
 
 # what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth, its readout
@@ -123,13 +126,14 @@ def _metric_options(object_metrics) -> Optional[dict]:
     return {"shrink": float(opts.get("shrink", 1.0)), "regions": bool(opts.get("regions", True))}
 
 
-_CLOUD_KEYS = ("stride", "near", "far", "min_confidence", "max_std", "capacity", "colour", "pixel")
+_CLOUD_KEYS = ("stride", "near", "far", "min_confidence", "max_std", "capacity", "colour", "pixel", "normals")
+_NORMAL_KEYS = ("radius", "edge_ratio", "near", "far", "picture", "valid")
 
 
 def _cloud_options(point_cloud, min_depth: float, max_depth: float) -> Optional[dict]:
     """The ``point_cloud`` keyword of both predictors: None (no cloud) or a dict with some of ``_CLOUD_KEYS``.  Defaults: every pixel
     (stride (1, 1)) within the dataset's depth range, no uncertainty filter, capacity = the strided grid's size (None here: the map's
-    size is known at the call), the frame's colour in every record, no pixel index."""
+    size is known at the call), the frame's colour in every record, no pixel index, no normal per point."""
     if point_cloud is None:
         return None
     opts = dict(point_cloud)
@@ -147,6 +151,36 @@ def _cloud_options(point_cloud, min_depth: float, max_depth: float) -> Optional[
            "capacity": None if cap is None else int(cap), "colour": bool(opts.get("colour", True)), "pixel": bool(opts.get("pixel", False))}
     if not out["near"] <= out["far"]:
         raise ValueError(f"point_cloud: near = {out['near']} must be <= far = {out['far']}")
+    return out
+
+
+def _cloud_normals(point_cloud) -> bool:
+    """The ``normals`` option of the ``point_cloud`` keyword (kept beside the cloud's own options, which are what they were)."""
+    return point_cloud is not None and bool(dict(point_cloud).get("normals", False))
+
+
+def _normal_options(surface_normals, cloud_normals: bool, min_depth: float, max_depth: float) -> Optional[dict]:
+    """The ``surface_normals`` keyword of both predictors: None (no normals -- unless the cloud's ``normals=True`` asks for them, which
+    implies the defaults) or a dict with some of ``_NORMAL_KEYS``.  Defaults: radius 2, edge_ratio 0.05, the dataset's depth range,
+    neither the picture nor the mask."""
+    if surface_normals is None:
+        if not cloud_normals:
+            return None
+        surface_normals = {}
+    opts = dict(surface_normals)
+    bad = set(opts) - set(_NORMAL_KEYS)
+    if bad:
+        raise ValueError(f"surface_normals: unknown option(s) {sorted(bad)}; expected some of {_NORMAL_KEYS}")
+    radius = opts.get("radius", DEFAULT_RADIUS)
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= hip_ops.NORMALS_MAX_RADIUS:
+        raise ValueError(f"surface_normals: radius must be an integer in 1..{hip_ops.NORMALS_MAX_RADIUS}, got {radius}")
+    out = {"radius": int(radius), "edge_ratio": float(opts.get("edge_ratio", DEFAULT_EDGE_RATIO)),
+           "near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth)),
+           "picture": bool(opts.get("picture", False)), "valid": bool(opts.get("valid", False))}
+    if not out["edge_ratio"] > 0.0:
+        raise ValueError(f"surface_normals: edge_ratio must be > 0, got {out['edge_ratio']}")
+    if not out["near"] <= out["far"]:
+        raise ValueError(f"surface_normals: near = {out['near']} must be <= far = {out['far']}")
     return out
 
 
@@ -261,7 +295,7 @@ class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
     def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None,
-                 object_metrics=None, resize=None, pixel_format=None):
+                 object_metrics=None, resize=None, pixel_format=None, surface_normals=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.fmt = None if pixel_format is None else PixelFormat.of(pixel_format)      # None: rgb24 through the rgb24 calls
         self.resize = _model_size(resize)
@@ -269,6 +303,8 @@ class _Ends:
         self.errors = _metric_options(object_metrics)
         self.min_depth, self.max_depth = _depth_range(args)
         self.cloud = _cloud_options(point_cloud, self.min_depth, self.max_depth)
+        self.cloud_normals = _cloud_normals(point_cloud)          # a normal per point of the cloud
+        self.normals = _normal_options(surface_normals, self.cloud_normals, self.min_depth, self.max_depth)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -385,8 +421,8 @@ class _Ends:
 
     def intrinsics_on(self, intrinsics, device, B: int) -> Optional[torch.Tensor]:
         """The intrinsics of a step -- a [B, 4] tensor or a list of per-frame 4-vectors, fx, fy, cx, cy in pixels of the SOURCE frames --
-        as fp32 [B, 4] on the device, or None without the ``point_cloud`` keyword / without intrinsics."""
-        if self.cloud is None or intrinsics is None:
+        as fp32 [B, 4] on the device, or None without intrinsics / with neither the ``point_cloud`` nor the ``surface_normals`` keyword."""
+        if (self.cloud is None and self.normals is None) or intrinsics is None:
             return None
         if not isinstance(intrinsics, torch.Tensor):
             intrinsics = torch.stack([torch.as_tensor(k, dtype=torch.float32).reshape(-1).cpu() for k in intrinsics], 0)
@@ -402,7 +438,12 @@ class _Ends:
         return ent[key]
 
     def points_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor]) -> PointCloud:
-        """The point cloud of a step's final map: one launch pair per entry of ``frames`` (a list of differently sized frames has an
+        """The point cloud of a step's final map (``_cloud_of``'s, as the caller asked for it)."""
+        return self._cloud_of(maps, K, frames)[0]
+
+    def _cloud_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor]) -> Tuple[PointCloud, Optional[torch.Tensor]]:
+        """(the point cloud, its pixel index -- made for the cloud's ``normals=True`` even when ``pixel`` was not asked for, and then not
+        handed out with the cloud).  The point cloud of a step's final map: one launch pair per entry of ``frames`` (a list of differently sized frames has an
         origin -- hence a principal point -- and a colour source per frame) into one set of buffers.  K is shifted by each frame's
         window origin (``point_cloud.shift_intrinsics``'s statement, the offsets cached on the device).  With a ``pixel_format`` other
         than rgb24 the colour is read from the window's RGB24 copy, made by one more launch in front (``hip_ops.frames_to_rgb24``):
@@ -414,7 +455,8 @@ class _Ends:
         dev = depth.device
         bufs = {"points": torch.empty((B, cap, 4), dtype=torch.float32, device=dev),
                 "counts": torch.empty((B,), dtype=torch.int32, device=dev), "total": torch.empty((B,), dtype=torch.int32, device=dev)}
-        if c["pixel"]:
+        want_pixel = c["pixel"] or self.cloud_normals
+        if want_pixel:
             bufs["pixel"] = torch.empty((B, cap), dtype=torch.int32, device=dev)
         conf = maps.get("confidence")
         std = maps.get("depth_std") if c["max_std"] < float("inf") else None
@@ -428,9 +470,33 @@ class _Ends:
             hip_ops.depth_unproject(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), cap, stride=c["stride"], near=c["near"],
                                     far=c["far"], confidence=None if conf is None else conf[i:i + n], min_confidence=c["min_confidence"],
                                     depth_std=None if std is None else std[i:i + n], max_std=c["max_std"],
-                                    frames=colour, top=ctop, left=cleft, want_pixel=c["pixel"], out=bufs, image_index=i)
+                                    frames=colour, top=ctop, left=cleft, want_pixel=want_pixel, out=bufs, image_index=i)
             i += n
-        return PointCloud(bufs["points"], bufs["counts"], bufs["total"], bufs.get("pixel"))
+        return PointCloud(bufs["points"], bufs["counts"], bufs["total"], bufs.get("pixel") if c["pixel"] else None), bufs.get("pixel")
+
+    def normals_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor], cloud: Optional[PointCloud] = None,
+                   pixel: Optional[torch.Tensor] = None) -> SurfaceNormals:
+        """The surface normals of a step's final map (Statement N, objcavit_amd/surface_normals.py): one launch per entry of ``frames``
+        into one set of buffers, K shifted by each frame's window origin exactly as ``points_of`` shifts it; they read the final map only,
+        so the frames' sizes, ``resize`` and ``pixel_format`` do not matter.  With the cloud's ``normals=True`` one more launch gathers a
+        normal per point of ``cloud`` through its ``pixel`` index."""
+        o, depth = self.normals, maps["depth"]
+        B, _, H, W = (int(v) for v in depth.shape)
+        dev = depth.device
+        want = ("normals",) + (("rgb8",) if o["picture"] else ()) + (("valid",) if o["valid"] else ())
+        shapes = {"normals": ((B, 3, H, W), torch.float32), "rgb8": ((B, H, W, 3), torch.uint8), "valid": ((B, H, W), torch.uint8)}
+        bufs = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
+        i = 0
+        for f in frames:
+            n = int(f.shape[0])
+            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
+            hip_ops.depth_normals(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), radius=o["radius"], near=o["near"], far=o["far"],
+                                  edge_ratio=o["edge_ratio"], want=want, out=bufs, image_index=i)
+            i += n
+        points = None
+        if cloud is not None and pixel is not None:
+            points = hip_ops.normals_gather(bufs["normals"], pixel, cloud.counts)
+        return SurfaceNormals(bufs["normals"], bufs.get("rgb8"), bufs.get("valid"), points)
 
     def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int,
                want: Tuple[str, ...], boxes=None, cloud=None) -> PredictResult:
@@ -439,8 +505,9 @@ class _Ends:
         (``boxes_on``'s pair): with the ``object_depth`` keyword the per-object readout right behind the final map, which is then made
         even if ``want`` leaves it out; with the ``object_metrics`` keyword and ground truth the per-object error right behind the metric
         launch, from the tensors that launch reads.
-        ``cloud`` = (K of the source frames [B, 4], the frames): the point cloud behind the map (and behind the readout), with the
-        maps its filters read made likewise."""
+        ``cloud`` = (K of the source frames [B, 4], the frames): with the ``point_cloud`` keyword the point cloud behind the map (and behind
+        the readout), with the maps its filters read made likewise; with the ``surface_normals`` keyword (or the cloud's ``normals=True``)
+        the normals behind the cloud."""
         asked = want
         errors = boxes if (self.errors is not None and depth_gt is not None) else None
         boxes = boxes if self.readout is not None else None
@@ -471,7 +538,12 @@ class _Ends:
         objects = None
         if boxes is not None:
             objects = object_depths(maps["depth"], boxes, depth_std=maps.get("depth_std") if "depth_std" in asked else None, **self.readout)
-        return _ObjectsResult(*res, objects=objects, points=None if cloud is None else self.points_of(maps, *cloud), object_metrics=table)
+        points = pixel = normals = None
+        if cloud is not None and self.cloud is not None:
+            points, pixel = self._cloud_of(maps, *cloud)
+        if cloud is not None and self.normals is not None:
+            normals = self.normals_of(maps, *cloud, cloud=points, pixel=pixel if self.cloud_normals else None)
+        return _ObjectsResult(*res, objects=objects, points=points, object_metrics=table, normals=normals)
 
 
 def _need_stats(want) -> bool:
@@ -543,6 +615,14 @@ class Predictor:
     otherwise).  ``min_confidence > 0`` / a finite ``max_std`` make the "confidence" / "depth_std" maps for the filter (``bin_stats`` is
     turned on) even when ``want`` leaves them out; byte 15 of a record is the confidence whenever that map is made, else 255.  Rows of
     ``points.points`` at or beyond ``points.counts[b]`` are not written.  ``boxes`` and ``intrinsics`` are keyword arguments.
+    ``surface_normals``: None, or a dict with some of ``radius`` (1..4, default 2), ``edge_ratio`` (default 0.05), ``near`` / ``far``
+    (default the dataset's depth range), ``picture`` (the rgb8 normal map), ``valid`` (the uint8 mask) -- the orientation of the surface
+    at every pixel (objcavit_amd/surface_normals.py, Statement N).  With it, ``intrinsics=`` of a call is read by one more launch behind
+    the finalize launch, beside the point cloud, and the result's ``normals`` ATTRIBUTE holds the ``SurfaceNormals`` (None otherwise);
+    K is shifted by each frame's window origin as for the cloud; the fp32 map is made for it even when ``want`` leaves "depth" out.
+    ``point_cloud=dict(..., normals=True)`` also gathers a normal per point into ``normals.points`` [B, capacity, 4], row for row with
+    ``points.points`` (a kept point at a pixel without a normal carries zeros; the cloud itself is unchanged), and implies
+    ``surface_normals={}`` when that keyword is absent.  Pass it by keyword.
     ``object_metrics``: None, or a dict with some of ``shrink`` / ``regions`` -- the depth error per box and over objects against
     background (objcavit_amd/object_metrics.py).  With it, a call that has both ``depth_gt`` and ``boxes=`` (in pixels of the ground
     truth's grid) issues one more call right behind the metric launch, on the tensors that launch reads, and the result's
@@ -550,12 +630,12 @@ class Predictor:
     by keyword."""
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
-                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, pixel_format=None,
+                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
         self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
-                          pixel_format)
+                          pixel_format, surface_normals)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -592,7 +672,8 @@ class PipelinedPredictor(_SlotPipeline):
     None unless ``want`` names "bin_edges" (the graph's static tensor is then copied per step).  Wants ``GPU_MAX_HW_QUEUES`` >= slots
     set before the HIP runtime starts, like ``PipelinedValidation``.  ``object_depth`` / ``submit(..., boxes=)``: as ``Predictor``'s; the
     readout runs on the slot's stream, a re-run step is read out from the re-run's map.  ``point_cloud`` / ``submit(..., intrinsics=)``:
-    likewise; a list of differently sized frames gives one launch pair per frame.  ``object_metrics``: as ``Predictor``'s, on the slot's
+    likewise; a list of differently sized frames gives one launch pair per frame.  ``surface_normals``: as ``Predictor``'s, on the slot's
+    stream behind the cloud, no host read.  ``object_metrics``: as ``Predictor``'s, on the slot's
     stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
     graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
@@ -609,14 +690,14 @@ class PipelinedPredictor(_SlotPipeline):
 
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
-                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, pixel_format=None,
+                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
         self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
-                          pixel_format)
+                          pixel_format, surface_normals)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
@@ -670,7 +751,8 @@ class PipelinedPredictor(_SlotPipeline):
         self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames), size), first_image_id,
                      (object_features, object_xywh_list))
         made = self._pending[-1].result
-        for t in tuple(getattr(made, "points", None) or ()) + tuple((getattr(made, "object_metrics", None) or ())[:2]):
+        for t in (tuple(getattr(made, "points", None) or ()) + tuple((getattr(made, "object_metrics", None) or ())[:2]) +
+                  tuple(getattr(made, "normals", None) or ())):
             if t is not None:                                # made on the slot's stream, read by the caller on this one
                 t.record_stream(torch.cuda.current_stream(t.device))
 
