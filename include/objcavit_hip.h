@@ -43,7 +43,8 @@ typedef void* ocv_stream_t;
  * ocv_conv3x3_packed_taps_k / ocv_conv3x3_split_packed_taps_fwd; nothing removed or changed: a caller built against 4 keeps working;
  * later ADDED (still 5: a new symbol changes nothing for an existing caller) ocv_conv3x3_nhwc_strided_fwd (EfficientNetV2),
  * ocv_depth_metrics_loss_workspace_bytes / ocv_depth_metrics_loss_fwd (validation loss),
- * ocv_depth_normals_fwd / ocv_normals_gather_fwd (surface normals of the final map, Statement N);
+ * ocv_depth_normals_fwd / ocv_normals_gather_fwd (surface normals of the final map, Statement N),
+ * ocv_ground_grid_workspace_bytes / ocv_ground_grid_fwd (bird's-eye occupancy grid of the final map, Statement G);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -875,6 +876,49 @@ int ocv_depth_normals_fwd(const float* depth, const float* K, int H, int W, int 
  * -1 with a message before the launch on: a null pointer, non-positive sizes, H * W or B * cap at or above 2^31, a misaligned pointer. */
 int ocv_normals_gather_fwd(const float* normals, const int* pixel, const int* counts, int H, int W, int cap, float* out, int B,
                            ocv_stream_t stream);
+/* Bird's-eye occupancy grid of the final map, STATEMENT G (no counterpart in the reference; the statement the tests compare against is
+ * tests/ground_grid_ref.py, fp32 torch on the CPU with one eager op per rounding: the kernel matches it EXACTLY, not within a tolerance).
+ * INPUTS  depth fp32 [B][1][H][W] (the map of ocv_depth_finalize_fwd); K fp32 [B][4] in DEVICE memory, as ocv_depth_unproject_fwd takes
+ * it; pose fp32 [B][12] in DEVICE memory, 16-byte aligned: a row-major 3 x 4 [R | t] from the camera frame (x right, y down, z forward)
+ * to the ground frame, row 0 = ground x (lateral, right), row 1 = ground y (forward), row 2 = height (up); confidence / depth_std
+ * (nullable, depth's shape) with min_confidence / max_std; the stride sy, sx and near <= far; the grid x0, y0, cell (metres, x0 and y0
+ * finite, cell > 0 and finite) and GX x GY cells (lateral x forward, each at most 2^24); the height band lo <= hi, both of magnitude at
+ * most 1000; obstacle_height (not NaN); min_points >= 1, min_obstacle_points >= 1.
+ * PER PIXEL.  A pixel is a candidate iff ocv_depth_unproject_fwd's predicate keeps it (the same rule, word for word, with its bad-camera
+ * rule: csrc/keep_pixel.hpp is included by both) and all twelve pose values of its image are finite (else the image keeps nothing).  For
+ * a candidate every operation is fp32 and rounded on its own, `/` the IEEE division:
+ *   rx = (float(x) - cx) / fx,  ry = (float(y) - cy) / fy,  X = rx * z,  Y = ry * z,  Z = z
+ *   g_i = ((p[i][0] * X + p[i][1] * Y) + p[i][2] * Z) + p[i][3]   for i = 0, 1, 2, summed left to right
+ *   fxi = floorf((g_0 - x0) / cell),  fyi = floorf((g_1 - y0) / cell)
+ *   in the grid iff 0 <= fxi < GX and 0 <= fyi < GY (compared as floats: NaN fails);  in the band iff lo <= g_2 <= hi.
+ * A point in the grid and in the band belongs to cell (iy, ix) = (int(fyi), int(fxi)).
+ * PER CELL, over its points:  count int32;  obstacle int32 = the points with g_2 > obstacle_height;  h_min, h_max fp32 = the extremes of
+ * g_2 (0 where count = 0: count = 0 is the flag);  h_mean: q = (long long)rintf(g_2 * 1024.f) (exact, at most 2^20 in magnitude) summed
+ * in int64, h_mean = (float)((double)sum / (1024.0 * count)), 0 where empty;  state uint8: 0 = unknown (count < min_points), 2 = occupied
+ * (not unknown and obstacle >= min_obstacle_points), 1 = free otherwise.
+ * PER LATERAL COLUMN:  first_occupied fp32 [B][GX] = y0 + float(iy) * cell (two fp32 roundings) of the smallest iy with state 2, +inf
+ * when the column has no occupied cell.
+ * OUTPUTS, each nullable, at least one given, EVERY element of a given output written:  count, obstacle int32 [B][GY][GX];  h_min, h_max,
+ * h_mean fp32 [B][GY][GX];  state uint8 [B][GY][GX];  first_occupied fp32 [B][GX].
+ * workspace: ocv_ground_grid_workspace_bytes(B, GX, GY) = 24 bytes per cell (0 for sizes the entry point refuses), 8-byte aligned.
+ * At most three launches on the stream (csrc/ground_grid.hip): a zero fill of the per-cell records in the workspace; the accumulate pass,
+ * one 256-thread workgroup per (image, tile of OCV_GROUND_GRID_TILE consecutive candidates of the strided grid), which merges its points
+ * on chip (equal-cell runs of a wave by a segmented reduction, then an LDS table keyed by cell) and issues one set of global atomics per
+ * distinct cell of the tile; the finalize pass with the column scan.  INTEGER atomics only (integer adds, unsigned max on the
+ * order-preserving integer image of the float, a 64-bit integer add): two calls give identical bytes whatever the arrival order.  No
+ * allocation, no synchronisation, nothing read on the host (capturable).  Images are independent: a batch can be filled by one call per
+ * image with offset pointers.
+ * -1 with a message before any launch on: a null depth / K / pose / workspace, all outputs null, non-positive sizes, H * W, B * tiles or
+ * B * GX * GY at or above 2^31, GX or GY above 2^24, a stride below 1, near > far, lo > hi, a band beyond +-1000, cell <= 0 or infinite,
+ * an infinite origin (or a NaN in any of these or in obstacle_height), min_points or min_obstacle_points below 1, K / pose not 16-byte
+ * aligned, the workspace not 8-byte aligned, another pointer not 4-byte aligned, a workspace that is too small. */
+#define OCV_GROUND_GRID_TILE 1024
+size_t ocv_ground_grid_workspace_bytes(int B, int GX, int GY);
+int ocv_ground_grid_fwd(const float* depth, const float* K, const float* pose, const float* confidence, const float* depth_std, int B, int H,
+                        int W, int sy, int sx, float near, float far, float min_confidence, float max_std, float x0, float y0, float cell,
+                        int GX, int GY, float lo, float hi, float obstacle_height, int min_points, int min_obstacle_points, int* count,
+                        int* obstacle, float* h_min, float* h_max, float* h_mean, uint8_t* state, float* first_occupied, void* workspace,
+                        size_t workspace_bytes, ocv_stream_t stream);
 /* Depth ERROR per detection box, and over objects against background: the validation metrics of ocv_depth_metrics_fwd, segmented by the
  * boxes of ocv_object_depth_fwd (no counterpart in the reference; the statement the tests compare against is tests/object_metrics_ref.py).
  * pred, pred_mirror (nullable, still mirrored), h, w, gt, H, W, min_depth, max_depth and the crop box: exactly as ocv_depth_metrics_fwd

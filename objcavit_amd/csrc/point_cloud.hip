@@ -15,6 +15,7 @@
 // per kept point, ~25 VALU instructions against 20 - 40 bytes of memory traffic: the launch is bound by its traffic).
 #include "common.hpp"
 #include "../../include/objcavit_hip.h"
+#include "keep_pixel.hpp"
 
 #include <float.h>
 
@@ -35,14 +36,12 @@ struct UnprojectArgs {
   float near, far, min_conf, max_std;
 };
 
-__device__ __forceinline__ bool up_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
 // The keepers of the calling thread's eight candidates of tile t of image b: bit r of the result = round r; z / cf / off of a keeper are
 // its depth, its confidence (1 without a map) and its pixel index y * W + x.  Everything the two kernels must agree on is here.
 __device__ __forceinline__ unsigned up_evaluate(const UnprojectArgs& p, int b, int t, int tid, float (&z)[UP_ROUNDS], float (&cf)[UP_ROUNDS],
                                                 int (&off)[UP_ROUNDS]) {
   const float4 k = *reinterpret_cast<const float4*>(p.K + 4 * (long)b);
-  const bool camera = up_finite(k.x) && k.x > 0.f && up_finite(k.y) && k.y > 0.f && up_finite(k.z) && up_finite(k.w);
+  const bool camera = up_camera_ok(k);                                      // (keep_pixel.hpp: the rule the ground grid shares)
   const long plane = (long)b * p.H * p.W;
   const unsigned c0 = (unsigned)t * UP_TILE + tid;
   int yc = (int)(c0 / (unsigned)p.Wc), xc = (int)(c0 - (unsigned)yc * p.Wc);
@@ -66,9 +65,7 @@ __device__ __forceinline__ unsigned up_evaluate(const UnprojectArgs& p, int b, i
   unsigned keep = 0u;
 #pragma unroll
   for (int r = 0; r < UP_ROUNDS; ++r) {
-    bool on = in[r] && up_finite(z[r]) && p.near <= z[r] && z[r] <= p.far;
-    if (p.conf != nullptr) on = on && cf[r] >= p.min_conf;                   // (NaN fails both)
-    if (p.std != nullptr) on = on && sd[r] <= p.max_std;
+    const bool on = up_keep(in[r], z[r], cf[r], sd[r], p.conf != nullptr, p.std != nullptr, p.near, p.far, p.min_conf, p.max_std);
     keep |= on ? 1u << r : 0u;
   }
   return keep;

@@ -1,7 +1,7 @@
 """hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip; a window of any size
 resized to the model's on the way in: csrc/frame_resize.hip), full-resolution depth
 maps out (csrc/depth_finalize.hip), and what is read out of the final map behind them: per-box statistics (csrc/object_depth.hip), the
-point cloud (csrc/point_cloud.hip), the surface normals (csrc/surface_normals.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
+point cloud (csrc/point_cloud.hip), the surface normals (csrc/surface_normals.hip), the bird's-eye occupancy grid (csrc/ground_grid.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
 static input)."""
 from __future__ import annotations
@@ -744,7 +744,104 @@ def normals_gather(normals: torch.Tensor, pixel: torch.Tensor, counts: torch.Ten
     return out
 
 
+GROUND_GRID_WANT = ("count", "obstacle", "h_min", "h_max", "h_mean", "state", "first_occupied")
+GROUND_GRID_TILE = 1024           # include/objcavit_hip.h: OCV_GROUND_GRID_TILE, candidates of the strided grid per workgroup
+GROUND_GRID_MAX_HEIGHT = 1000.0   # Statement G: the band's edges are of magnitude at most 1000 (a point's height in 1 / 1024 m fits 2^20)
+
+
+def ground_grid(depth: torch.Tensor, K: torch.Tensor, pose: torch.Tensor, grid: Tuple[float, float, float, int, int],
+                band: Tuple[float, float] = (-0.5, 2.5), obstacle_height: float = 0.3, min_points: int = 1, min_obstacle_points: int = 3,
+                stride: Tuple[int, int] = (1, 1), near: float = 0.0, far: float = float("inf"), confidence: Optional[torch.Tensor] = None,
+                min_confidence: float = 0.0, depth_std: Optional[torch.Tensor] = None, max_std: float = float("inf"),
+                want: Tuple[str, ...] = GROUND_GRID_WANT, out: Optional[dict] = None, workspace: Optional[torch.Tensor] = None,
+                image_index: int = 0) -> dict:
+    """The final map as a bird's-eye occupancy grid (Statement G of include/objcavit_hip.h): ``depth`` fp32 [B, 1, H, W], ``K`` fp32
+    [B, 4] on the device as ``depth_unproject`` takes it, ``pose`` fp32 [B, 12] on the device = a row-major 3 x 4 [R | t] from the camera
+    frame (x right, y down, z forward) to the ground frame (row 0 lateral, row 1 forward, row 2 height), ``grid`` = (x0, y0, cell, GX,
+    GY): GX x GY cells of ``cell`` metres from the corner (x0, y0), lateral x forward.  A pixel is a point iff ``depth_unproject`` would
+    keep it (``stride``, ``near`` / ``far``, ``confidence`` / ``depth_std`` with their thresholds, a usable camera) and its image's pose
+    is finite; the point's ground coordinates g = R P + t are fp32, every operation rounded on its own; it belongs to cell
+    (floor((g_1 - y0) / cell), floor((g_0 - x0) / cell)) if that lies in the grid and ``band[0]`` <= g_2 <= ``band[1]``.  ->
+    {"count", "obstacle" (points above ``obstacle_height``): int32 [B, GY, GX]; "h_min", "h_max", "h_mean": fp32 [B, GY, GX], 0 in an
+    empty cell; "state": uint8 [B, GY, GX], 0 = unknown (count < min_points), 2 = occupied (obstacle >= min_obstacle_points), 1 = free;
+    "first_occupied": fp32 [B, GX], the forward distance y0 + iy * cell of the nearest occupied cell of a lateral column, +inf without
+    one}, those that ``want`` names; every element is written.  ``out``: {name: tensor} of caller-owned buffers [N, ...] with N >=
+    image_index + B; the B images are written at ``image_index`` and the dict returned holds the whole buffers.  ``workspace``: a uint8
+    device tensor of at least ``ocv_ground_grid_workspace_bytes`` (default: the stream's workspace store).  Three launches
+    (ocv_ground_grid_fwd) on the current stream, integer atomics only (two calls give the same bytes), nothing read on the host:
+    capturable with ``out`` and a warmed-up workspace."""
+    lib = _lib.load()
+    _req(depth, "depth")
+    if depth.dim() != 4 or depth.shape[1] != 1:
+        raise ValueError(f"ground_grid: expected depth [B, 1, H, W], got {tuple(depth.shape)}")
+    B, _, H, W = (int(s) for s in depth.shape)
+    _req(K, "K")
+    if tuple(K.shape) != (B, 4):
+        raise ValueError(f"ground_grid: K must be fp32 [{B}, 4] = fx, fy, cx, cy, got {tuple(K.shape)}")
+    _req(pose, "pose")
+    if tuple(pose.shape) != (B, 12):
+        raise ValueError(f"ground_grid: pose must be fp32 [{B}, 12] = a row-major 3 x 4 [R | t], got {tuple(pose.shape)}")
+    for name, t in (("confidence", confidence), ("depth_std", depth_std)):
+        if t is not None:
+            _req(t, name)
+            if t.shape != depth.shape:
+                raise ValueError(f"ground_grid: {name} must have depth's shape")
+    sy, sx = int(stride[0]), int(stride[1])
+    unproject_grid(H, W, (sy, sx))
+    if not float(near) <= float(far):
+        raise ValueError(f"ground_grid: near = {near} must be <= far = {far}")
+    if len(tuple(grid)) != 5:
+        raise ValueError(f"ground_grid: grid must be (x0, y0, cell, GX, GY), got {grid}")
+    x0, y0, cell = (C.c_float(float(v)).value for v in tuple(grid)[:3])
+    GX, GY = int(grid[3]), int(grid[4])
+    if GX != grid[3] or GY != grid[4] or GX < 1 or GY < 1:
+        raise ValueError(f"ground_grid: GX, GY must be integers >= 1, got {grid[3]}, {grid[4]}")
+    if not (0.0 < cell < float("inf")) or not abs(x0) < float("inf") or not abs(y0) < float("inf"):
+        raise ValueError(f"ground_grid: cell must be > 0 and finite and the origin finite, got {tuple(grid)[:3]}")
+    lo, hi = (C.c_float(float(v)).value for v in band)
+    if not lo <= hi or not abs(lo) <= GROUND_GRID_MAX_HEIGHT or not abs(hi) <= GROUND_GRID_MAX_HEIGHT:
+        raise ValueError(f"ground_grid: band must be (lo, hi) with lo <= hi, both within +-{GROUND_GRID_MAX_HEIGHT}, got {tuple(band)}")
+    if float(obstacle_height) != float(obstacle_height):
+        raise ValueError("ground_grid: obstacle_height is NaN")
+    if int(min_points) != min_points or int(min_obstacle_points) != min_obstacle_points or min_points < 1 or min_obstacle_points < 1:
+        raise ValueError(f"ground_grid: min_points and min_obstacle_points must be integers >= 1, got {min_points}, {min_obstacle_points}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(GROUND_GRID_WANT):
+        raise ValueError(f"ground_grid: want must name some of {GROUND_GRID_WANT} (got {want})")
+    out = dict(out or {})
+    N, index = B, int(image_index)
+    if out:
+        missing = [n for n in want if n not in out]
+        if missing:
+            raise ValueError(f"ground_grid: out has no {missing} (it needs {want})")
+        N = int(out[want[0]].shape[0]) if out[want[0]].dim() else 0
+        if index < 0 or index + B > N:
+            raise ValueError(f"ground_grid: {B} image(s) at index {index} do not fit buffers of {N}")
+    else:
+        index = 0
+    dtypes = {"count": torch.int32, "obstacle": torch.int32, "state": torch.uint8}
+    res = {n: _out_slice(out.get(n), (N, GX) if n == "first_occupied" else (N, GY, GX), dtypes.get(n, torch.float32), depth.device,
+                         "ground_grid") for n in GROUND_GRID_WANT if n in want}
+    at = {n: t.data_ptr() + index * t.element_size() * (GX if n == "first_occupied" else GX * GY) for n, t in res.items()}
+    need = int(lib.ocv_ground_grid_workspace_bytes(B, GX, GY))
+    if need == 0:
+        raise ValueError(f"ground_grid: a grid of {B} x {GY} x {GX} cells is too large (B * GX * GY below 2^31, GX and GY at most 2^24)")
+    if workspace is None:
+        from ._core import workspace as _workspace
+        workspace = _workspace(need, depth.device, "ground_grid")
+    else:
+        _req(workspace, "workspace", torch.uint8)
+    with timed("ground_grid"):
+        check(lib.ocv_ground_grid_fwd(depth.data_ptr(), K.data_ptr(), pose.data_ptr(), _ptr(confidence), _ptr(depth_std), B, H, W, sy, sx,
+                                      float(near), float(far), float(min_confidence), float(max_std), x0, y0, cell, GX, GY, lo, hi,
+                                      float(obstacle_height), int(min_points), int(min_obstacle_points), at.get("count"), at.get("obstacle"),
+                                      at.get("h_min"), at.get("h_max"), at.get("h_mean"), at.get("state"), at.get("first_occupied"),
+                                      workspace.data_ptr(), int(workspace.numel()), _stream()), "ocv_ground_grid_fwd")
+    return res
+
+
 __all__ = ["frame_ingest", "frame_ingest_format", "frame_resize_ingest_format", "frames_to_rgb24", "frame_yuv_tables", "resize_taps", "frame_resize_supported", "frame_resize_taps", "frame_resize_ingest", "FRAME_RESIZE_MAX_RATIO",
            "depth_ingest", "depth_finalize", "colormap_scale", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics",
            "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
-           "unproject_grid", "UNPROJECT_TILE", "depth_normals", "normals_gather", "NORMALS_WANT", "NORMALS_MAX_RADIUS"]
+           "unproject_grid", "UNPROJECT_TILE", "depth_normals", "normals_gather", "NORMALS_WANT", "NORMALS_MAX_RADIUS",
+           "ground_grid", "GROUND_GRID_WANT", "GROUND_GRID_TILE", "GROUND_GRID_MAX_HEIGHT"]

@@ -13,6 +13,7 @@ owns the slots, their streams and the range-guard handling; the pair forward is 
 """
 from __future__ import annotations
 
+import math
 from collections import namedtuple
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -25,6 +26,7 @@ from .object_metrics import ObjectMetrics, object_metrics as _object_metrics
 from .pixel_formats import PixelFormat, PlanarFrames
 from .point_cloud import PointCloud
 from .surface_normals import DEFAULT_EDGE_RATIO, DEFAULT_RADIUS, SurfaceNormals
+from .ground_grid import DEFAULTS as _GROUND_DEFAULTS, GroundGrid, grid_of as _grid_of, ground_pose as _ground_pose
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
@@ -40,29 +42,32 @@ PredictResult.objects = None                   # the per-object readout (an ``Ob
 PredictResult.points = None                    # the point cloud (a ``PointCloud``) or None: an attribute as well
 PredictResult.object_metrics = None            # the depth error per box / region (an ``ObjectMetrics``) or None: an attribute as well
 PredictResult.normals = None                   # the surface normals (a ``SurfaceNormals``) or None: an attribute as well
+PredictResult.ground = None                    # the bird's-eye occupancy grid (a ``GroundGrid``) or None: an attribute as well
 
 
 class _ObjectsResult(PredictResult):
-    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` / ``object_metrics`` / ``normals`` attributes hold
-    the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals``."""
+    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` / ``object_metrics`` / ``normals`` / ``ground``
+    attributes hold the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals`` / ``GroundGrid``."""
 
     def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, points: Optional[PointCloud] = None,
-                object_metrics: Optional[ObjectMetrics] = None, normals: Optional[SurfaceNormals] = None, **kw):
+                object_metrics: Optional[ObjectMetrics] = None, normals: Optional[SurfaceNormals] = None,
+                ground: Optional[GroundGrid] = None, **kw):
         self = super().__new__(cls, *fields, **kw)
         self.objects = objects
         self.points = points
         self.object_metrics = object_metrics
         self.normals = normals
+        self.ground = ground
         return self
 
     def _replace(self, **kw):
         return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects, points=self.points,
-                              object_metrics=self.object_metrics, normals=self.normals)
+                              object_metrics=self.object_metrics, normals=self.normals, ground=self.ground)
 
 
 # what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth, its readout
 # boxes and, for the point cloud, its intrinsics (of the source frames, on the device)
-_Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics", "size"], defaults=(None, None))     # size: the step's final size (``resize``)
+_Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics", "size", "camera_pose"], defaults=(None, None, None))     # size: the step's final size (``resize``)
 
 Frames = Union[torch.Tensor, PlanarFrames, Sequence[Union[torch.Tensor, PlanarFrames]]]
 
@@ -128,6 +133,8 @@ def _metric_options(object_metrics) -> Optional[dict]:
 
 _CLOUD_KEYS = ("stride", "near", "far", "min_confidence", "max_std", "capacity", "colour", "pixel", "normals")
 _NORMAL_KEYS = ("radius", "edge_ratio", "near", "far", "picture", "valid")
+_GROUND_KEYS = ("cell", "x_range", "y_range", "height", "pitch", "roll", "band", "obstacle_height", "min_points", "min_obstacle_points",
+                "stride", "near", "far", "min_confidence", "max_std", "want")
 
 
 def _cloud_options(point_cloud, min_depth: float, max_depth: float) -> Optional[dict]:
@@ -181,6 +188,50 @@ def _normal_options(surface_normals, cloud_normals: bool, min_depth: float, max_
         raise ValueError(f"surface_normals: edge_ratio must be > 0, got {out['edge_ratio']}")
     if not out["near"] <= out["far"]:
         raise ValueError(f"surface_normals: near = {out['near']} must be <= far = {out['far']}")
+    return out
+
+
+def _ground_options(ground_grid, min_depth: float, max_depth: float) -> Optional[dict]:
+    """The ``ground_grid`` keyword of both predictors: None (no grid) or a dict with some of ``_GROUND_KEYS``.  Defaults: cells of 0.1 m
+    over 20 m x 40 m in front of a level camera 1.65 m above the ground, the band -0.5 .. 2.5 m, obstacles above 0.3 m, a cell known
+    from one point on and occupied from three obstacle points on; every pixel within the dataset's depth range, no uncertainty filter,
+    every output.  -> the options with ``grid`` = (x0, y0, cell, GX, GY) and ``pose`` = the keyword's pose, fp32 [1, 12] on the host."""
+    if ground_grid is None:
+        return None
+    opts = dict(ground_grid)
+    bad = set(opts) - set(_GROUND_KEYS)
+    if bad:
+        raise ValueError(f"ground_grid: unknown option(s) {sorted(bad)}; expected some of {_GROUND_KEYS}")
+    d = _GROUND_DEFAULTS
+    stride = opts.get("stride", (1, 1))
+    stride = (int(stride), int(stride)) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
+    hip_ops.unproject_grid(1, 1, stride)
+    band = tuple(float(v) for v in opts.get("band", d["band"]))
+    limit = hip_ops.GROUND_GRID_MAX_HEIGHT
+    if len(band) != 2 or not band[0] <= band[1] or not abs(band[0]) <= limit or not abs(band[1]) <= limit:
+        raise ValueError(f"ground_grid: band must be (lo, hi) with lo <= hi, both within +-{limit}, got {opts.get('band')}")
+    counts = {}
+    for name in ("min_points", "min_obstacle_points"):
+        v = opts.get(name, d[name])
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"ground_grid: {name} must be an integer >= 1, got {v}")
+        counts[name] = int(v)
+    want = opts.get("want", hip_ops.GROUND_GRID_WANT)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(hip_ops.GROUND_GRID_WANT):
+        raise ValueError(f"ground_grid: want must name some of {hip_ops.GROUND_GRID_WANT} (got {want})")
+    angles = [float(opts.get(name, d[name])) for name in ("height", "pitch", "roll")]
+    if not all(math.isfinite(v) for v in angles):
+        raise ValueError(f"ground_grid: height, pitch and roll must be finite, got {angles}")
+    out = {"grid": _grid_of(opts.get("cell", d["cell"]), opts.get("x_range", d["x_range"]), opts.get("y_range", d["y_range"])),
+           "pose": _ground_pose(*angles), "band": band, "obstacle_height": float(opts.get("obstacle_height", d["obstacle_height"])),
+           "stride": stride, "near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth)),
+           "min_confidence": float(opts.get("min_confidence", 0.0)), "max_std": float(opts.get("max_std", float("inf"))),
+           "want": tuple(n for n in hip_ops.GROUND_GRID_WANT if n in want), **counts}
+    if out["obstacle_height"] != out["obstacle_height"]:
+        raise ValueError("ground_grid: obstacle_height is NaN")
+    if not out["near"] <= out["far"]:
+        raise ValueError(f"ground_grid: near = {out['near']} must be <= far = {out['far']}")
     return out
 
 
@@ -295,7 +346,7 @@ class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
     def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None,
-                 object_metrics=None, resize=None, pixel_format=None, surface_normals=None):
+                 object_metrics=None, resize=None, pixel_format=None, surface_normals=None, ground_grid=None):
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.fmt = None if pixel_format is None else PixelFormat.of(pixel_format)      # None: rgb24 through the rgb24 calls
         self.resize = _model_size(resize)
@@ -305,6 +356,7 @@ class _Ends:
         self.cloud = _cloud_options(point_cloud, self.min_depth, self.max_depth)
         self.cloud_normals = _cloud_normals(point_cloud)          # a normal per point of the cloud
         self.normals = _normal_options(surface_normals, self.cloud_normals, self.min_depth, self.max_depth)
+        self.ground = _ground_options(ground_grid, self.min_depth, self.max_depth)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -421,14 +473,60 @@ class _Ends:
 
     def intrinsics_on(self, intrinsics, device, B: int) -> Optional[torch.Tensor]:
         """The intrinsics of a step -- a [B, 4] tensor or a list of per-frame 4-vectors, fx, fy, cx, cy in pixels of the SOURCE frames --
-        as fp32 [B, 4] on the device, or None without intrinsics / with neither the ``point_cloud`` nor the ``surface_normals`` keyword."""
-        if (self.cloud is None and self.normals is None) or intrinsics is None:
+        as fp32 [B, 4] on the device, or None without intrinsics / with none of the ``point_cloud``, ``surface_normals`` and
+        ``ground_grid`` keywords."""
+        if (self.cloud is None and self.normals is None and self.ground is None) or intrinsics is None:
             return None
         if not isinstance(intrinsics, torch.Tensor):
             intrinsics = torch.stack([torch.as_tensor(k, dtype=torch.float32).reshape(-1).cpu() for k in intrinsics], 0)
         if tuple(intrinsics.shape) != (B, 4):
             raise ValueError(f"intrinsics: one (fx, fy, cx, cy) per frame ([{B}, 4]), got {tuple(intrinsics.shape)}")
         return intrinsics.to(device=device, dtype=torch.float32).contiguous()
+
+    def pose_on(self, camera_pose, device, B: int) -> Optional[torch.Tensor]:
+        """The camera poses of a step -- a [B, 12] (or [B, 3, 4]) tensor or a list of per-frame 3 x 4 [R | t], camera frame to ground
+        frame -- as fp32 [B, 12] on the device, or None without them / without the ``ground_grid`` keyword (whose own pose then holds)."""
+        if self.ground is None or camera_pose is None:
+            return None
+        if not isinstance(camera_pose, torch.Tensor):
+            camera_pose = torch.stack([torch.as_tensor(p, dtype=torch.float32).reshape(-1).cpu() for p in camera_pose], 0)
+        if camera_pose.dim() == 3:
+            camera_pose = camera_pose.reshape(camera_pose.shape[0], -1)
+        if tuple(camera_pose.shape) != (B, 12):
+            raise ValueError(f"camera_pose: one row-major 3 x 4 [R | t] per frame ([{B}, 12]), got {tuple(camera_pose.shape)}")
+        return camera_pose.to(device=device, dtype=torch.float32).contiguous()
+
+    def ground_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor], pose: Optional[torch.Tensor] = None) -> GroundGrid:
+        """The bird's-eye occupancy grid of a step's final map (Statement G, objcavit_amd/ground_grid.py): one call (three launches) per
+        entry of ``frames`` into one set of buffers, K shifted by each frame's window origin exactly as ``_cloud_of`` shifts it.
+        ``pose``: the step's [B, 12] (``camera_pose=``); None: the keyword's pose for every image (uploaded once per device)."""
+        o, depth = self.ground, maps["depth"]
+        B = int(depth.shape[0])
+        dev = depth.device
+        x0, y0, cell, GX, GY = o["grid"]
+        if pose is None:
+            ent = self._on(dev, False)
+            key = ("ground_pose", B)
+            if key not in ent:
+                ent[key] = o["pose"].expand(B, 12).contiguous().to(dev)
+            pose = ent[key]
+        dtypes = {"count": torch.int32, "obstacle": torch.int32, "state": torch.uint8}
+        bufs = {n: torch.empty((B, GX) if n == "first_occupied" else (B, GY, GX), dtype=dtypes.get(n, torch.float32), device=dev)
+                for n in o["want"]}
+        conf = maps.get("confidence") if o["min_confidence"] > 0.0 else None
+        std = maps.get("depth_std") if o["max_std"] < float("inf") else None
+        i = 0
+        for f in frames:
+            n = int(f.shape[0])
+            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
+            hip_ops.ground_grid(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), pose[i:i + n], o["grid"], band=o["band"],
+                                obstacle_height=o["obstacle_height"], min_points=o["min_points"],
+                                min_obstacle_points=o["min_obstacle_points"], stride=o["stride"], near=o["near"], far=o["far"],
+                                confidence=None if conf is None else conf[i:i + n], min_confidence=o["min_confidence"],
+                                depth_std=None if std is None else std[i:i + n], max_std=o["max_std"], want=o["want"], out=bufs,
+                                image_index=i)
+            i += n
+        return GroundGrid(*(bufs.get(n) for n in hip_ops.GROUND_GRID_WANT), x0=x0, y0=y0, cell=cell)
 
     def _shift(self, device, top: int, left: int) -> torch.Tensor:
         ent = self._on(device, False)
@@ -499,7 +597,7 @@ class _Ends:
         return SurfaceNormals(bufs["normals"], bufs.get("rgb8"), bufs.get("valid"), points)
 
     def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int,
-               want: Tuple[str, ...], boxes=None, cloud=None) -> PredictResult:
+               want: Tuple[str, ...], boxes=None, cloud=None, camera_pose=None) -> PredictResult:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
         the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  ``boxes``
         (``boxes_on``'s pair): with the ``object_depth`` keyword the per-object readout right behind the final map, which is then made
@@ -507,7 +605,8 @@ class _Ends:
         launch, from the tensors that launch reads.
         ``cloud`` = (K of the source frames [B, 4], the frames): with the ``point_cloud`` keyword the point cloud behind the map (and behind
         the readout), with the maps its filters read made likewise; with the ``surface_normals`` keyword (or the cloud's ``normals=True``)
-        the normals behind the cloud."""
+        the normals behind the cloud; with the ``ground_grid`` keyword the occupancy grid behind them, posed by ``camera_pose`` (fp32
+        [B, 12] on the device) or, without it, by the keyword's pose."""
         asked = want
         errors = boxes if (self.errors is not None and depth_gt is not None) else None
         boxes = boxes if self.readout is not None else None
@@ -515,6 +614,7 @@ class _Ends:
             want = want + ("depth",)
         if cloud is not None:
             want = want + tuple(w for w in _cloud_want(self.cloud) if w not in want)
+            want = want + tuple(w for w in _cloud_want(self.ground) if w not in want)
         pred = out.depth_pred.contiguous()
         mirror_pred = None if mirror is None else mirror.depth_pred.contiguous()
         edges = getattr(out, "bin_edges", None)
@@ -543,7 +643,10 @@ class _Ends:
             points, pixel = self._cloud_of(maps, *cloud)
         if cloud is not None and self.normals is not None:
             normals = self.normals_of(maps, *cloud, cloud=points, pixel=pixel if self.cloud_normals else None)
-        return _ObjectsResult(*res, objects=objects, points=points, object_metrics=table, normals=normals)
+        ground = None
+        if cloud is not None and self.ground is not None:
+            ground = self.ground_of(maps, *cloud, pose=camera_pose)
+        return _ObjectsResult(*res, objects=objects, points=points, object_metrics=table, normals=normals, ground=ground)
 
 
 def _need_stats(want) -> bool:
@@ -623,6 +726,15 @@ class Predictor:
     ``point_cloud=dict(..., normals=True)`` also gathers a normal per point into ``normals.points`` [B, capacity, 4], row for row with
     ``points.points`` (a kept point at a pixel without a normal carries zeros; the cloud itself is unchanged), and implies
     ``surface_normals={}`` when that keyword is absent.  Pass it by keyword.
+    ``ground_grid``: None, or a dict with some of ``cell`` (0.1 m), ``x_range`` ((-10, 10)), ``y_range`` ((0, 40)), ``height`` (1.65),
+    ``pitch`` / ``roll`` (0.0, radians: ``ground_grid.ground_pose``), ``band`` ((-0.5, 2.5)), ``obstacle_height`` (0.3), ``min_points``
+    (1), ``min_obstacle_points`` (3), ``stride``, ``near`` / ``far`` (default the dataset's depth range), ``min_confidence`` /
+    ``max_std`` (as the cloud's: the maps are made for the filter even when ``want`` leaves them out), ``want`` (a subset of the
+    outputs) -- the bird's-eye occupancy grid of the final map (objcavit_amd/ground_grid.py, Statement G).  With it, ``intrinsics=`` of a
+    call is read by three more launches behind the finalize launch, and the result's ``ground`` ATTRIBUTE holds the ``GroundGrid`` (None
+    otherwise); K is shifted by each frame's window origin as for the cloud.  ``camera_pose=`` of a call -- fp32 [B, 12] (or [B, 3, 4],
+    or a list of 3 x 4), camera frame to ground frame -- replaces the keyword's pose for that call (an IMU's pose per frame).  Pass both
+    by keyword.
     ``object_metrics``: None, or a dict with some of ``shrink`` / ``regions`` -- the depth error per box and over objects against
     background (objcavit_amd/object_metrics.py).  With it, a call that has both ``depth_gt`` and ``boxes=`` (in pixels of the ground
     truth's grid) issues one more call right behind the metric launch, on the tensors that launch reads, and the result's
@@ -630,12 +742,13 @@ class Predictor:
     by keyword."""
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
-                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None, pixel_format=None,
+                 vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
+                 ground_grid: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
         self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
-                          pixel_format, surface_normals)
+                          pixel_format, surface_normals, ground_grid)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -649,9 +762,9 @@ class Predictor:
 
     @torch.no_grad()
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",),
-                 intrinsics=None, boxes=None) -> PredictResult:
+                 camera_pose=None, intrinsics=None, boxes=None) -> PredictResult:
         want = _check_want(want)
-        if _need_stats(want) or (intrinsics is not None and _cloud_want(self.ends.cloud)):
+        if _need_stats(want) or (intrinsics is not None and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground))):
             _turn_stats_on(self.model)
         frames = self.ends.frames_of(frames_u8, "frames_u8")
         B = sum(int(f.shape[0]) for f in frames)
@@ -659,7 +772,8 @@ class Predictor:
         out, mirror = self._forward(frames, B)
         K = self.ends.intrinsics_on(intrinsics, frames[0].device, B)
         return self.ends.finish(out, mirror, size, self.ends.ground_truth(depth_gt, B), first_image_id, want,
-                                self.ends.boxes_on(boxes, frames[0].device, B), None if K is None else (K, frames))
+                                self.ends.boxes_on(boxes, frames[0].device, B), None if K is None else (K, frames),
+                                self.ends.pose_on(camera_pose, frames[0].device, B))
 
 
 class PipelinedPredictor(_SlotPipeline):
@@ -673,7 +787,8 @@ class PipelinedPredictor(_SlotPipeline):
     set before the HIP runtime starts, like ``PipelinedValidation``.  ``object_depth`` / ``submit(..., boxes=)``: as ``Predictor``'s; the
     readout runs on the slot's stream, a re-run step is read out from the re-run's map.  ``point_cloud`` / ``submit(..., intrinsics=)``:
     likewise; a list of differently sized frames gives one launch pair per frame.  ``surface_normals``: as ``Predictor``'s, on the slot's
-    stream behind the cloud, no host read.  ``object_metrics``: as ``Predictor``'s, on the slot's
+    stream behind the cloud, no host read.  ``ground_grid`` / ``submit(..., camera_pose=)``: as ``Predictor``'s, on the slot's stream behind
+    the normals; the pose is uploaded in ``submit`` and held like the frames.  ``object_metrics``: as ``Predictor``'s, on the slot's
     stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
     graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
@@ -690,15 +805,16 @@ class PipelinedPredictor(_SlotPipeline):
 
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
-                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None, pixel_format=None,
+                 vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
+                 ground_grid: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
         self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
-                          pixel_format, surface_normals)
-        if _need_stats(self.want) or _cloud_want(self.ends.cloud):
+                          pixel_format, surface_normals, ground_grid)
+        if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
         ex = self.ends.frames_of(example_frames, "example_frames")
@@ -718,7 +834,8 @@ class PipelinedPredictor(_SlotPipeline):
     def _finish(self, out, step: _Step, first_image_id: int) -> PredictResult:
         gt = self.ends.ground_truth(step.depth_gt, self.B)
         out, mirror = _split(out, self.B) if self.flip_tta else (out, None)
-        res = self.ends.finish(out, mirror, step.size or self.size, gt, first_image_id, self.want, step.boxes, step.intrinsics)
+        res = self.ends.finish(out, mirror, step.size or self.size, gt, first_image_id, self.want, step.boxes, step.intrinsics,
+                               step.camera_pose)
         return res._replace(bin_edges=res.bin_edges.clone() if (self.want_edges and res.bin_edges is not None) else None)
 
     def collect(self) -> List[PredictResult]:
@@ -726,7 +843,7 @@ class PipelinedPredictor(_SlotPipeline):
         return self._collect()
 
     def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None,
-               intrinsics=None, boxes=None) -> None:
+               camera_pose=None, intrinsics=None, boxes=None) -> None:
         """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the boxes of the step's frames
         (``object_depth`` / ``object_metrics`` keywords); lists are padded here, on the caller's stream, and the tensors are held like the frames.
         ``intrinsics``: the frames' (fx, fy, cx, cy) for the point cloud (``point_cloud`` keyword), uploaded here and held likewise;
@@ -748,12 +865,14 @@ class PipelinedPredictor(_SlotPipeline):
         held += list(boxes or ())
         K = self.ends.intrinsics_on(intrinsics, frames[0].device, self.B)
         held += [] if K is None else [K]
-        self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames), size), first_image_id,
+        pose = self.ends.pose_on(camera_pose, frames[0].device, self.B)
+        held += [] if pose is None else [pose]
+        self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames), size, pose), first_image_id,
                      (object_features, object_xywh_list))
         made = self._pending[-1].result
         for t in (tuple(getattr(made, "points", None) or ()) + tuple((getattr(made, "object_metrics", None) or ())[:2]) +
-                  tuple(getattr(made, "normals", None) or ())):
-            if t is not None:                                # made on the slot's stream, read by the caller on this one
+                  tuple(getattr(made, "normals", None) or ()) + tuple(getattr(made, "ground", None) or ())):
+            if isinstance(t, torch.Tensor):                                # made on the slot's stream, read by the caller on this one
                 t.record_stream(torch.cuda.current_stream(t.device))
 
     def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
