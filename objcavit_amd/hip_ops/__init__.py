@@ -12,9 +12,10 @@ One module per kernel family (round 5; the single 2 100-line file of rounds 1 - 
     conv     hl32 split activations, split implicit-GEMM / Winograd / tap-form / exact convolutions, resize + concat + split
     heads    patch embedding, pixel-wise dot, bin head, bin edges, ragged object lists, positional-embedding samplers
     encoder  EfficientNet NHWC blocks (stem, 1x1, depthwise + squeeze-excite, fused expand + depthwise), validation metrics
-    frames   predict path: uint8 / uint16 frame ingest (crop, antialiased resize, normalise, mirror), final depth map (fp32, 16-bit, colour-mapped),
-             per-box depth statistics of the final map, the final map as compacted 3-D points, as surface normals and as a bird's-eye occupancy grid, depth error per box / region
-Every name stays reachable as ``hip_ops.<name>`` (this file re-exports the five modules' namespaces; state objects such as
+    frames   predict path: uint8 / uint16 frame ingest (crop, antialiased resize, normalise, mirror), final depth map (fp32, 16-bit, colour-mapped)
+    readouts behind the final map: per-box depth statistics, the map as compacted 3-D points, as surface normals and as a bird's-eye
+             occupancy grid, depth error per box / region
+Every name stays reachable as ``hip_ops.<name>`` (this file re-exports the modules' namespaces; state objects such as
 ``ROUTE_REPORT`` / ``_TLS`` are shared, not copied).
 """
 from ._core import *       # noqa: F401,F403
@@ -23,3 +24,4 @@ from .conv import *        # noqa: F401,F403
 from .heads import *       # noqa: F401,F403
 from .encoder import *     # noqa: F401,F403
 from .frames import *      # noqa: F401,F403
+from .readouts import *    # noqa: F401,F403

@@ -38,36 +38,6 @@ STATS_WANT = ("depth_std", "confidence")       # the outputs that need the model
 
 PredictResult = namedtuple("PredictResult", ["depth", "depth_u16", "rgb8", "records", "bin_edges", "depth_std", "confidence"],
                            defaults=(None, None))
-PredictResult.objects = None                   # the per-object readout (an ``ObjectDepths``) or None: an ATTRIBUTE, not a field
-PredictResult.points = None                    # the point cloud (a ``PointCloud``) or None: an attribute as well
-PredictResult.object_metrics = None            # the depth error per box / region (an ``ObjectMetrics``) or None: an attribute as well
-PredictResult.normals = None                   # the surface normals (a ``SurfaceNormals``) or None: an attribute as well
-PredictResult.ground = None                    # the bird's-eye occupancy grid (a ``GroundGrid``) or None: an attribute as well
-
-
-class _ObjectsResult(PredictResult):
-    """A ``PredictResult`` -- same fields, same tuple -- whose ``objects`` / ``points`` / ``object_metrics`` / ``normals`` / ``ground``
-    attributes hold the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals`` / ``GroundGrid``."""
-
-    def __new__(cls, *fields, objects: Optional[ObjectDepths] = None, points: Optional[PointCloud] = None,
-                object_metrics: Optional[ObjectMetrics] = None, normals: Optional[SurfaceNormals] = None,
-                ground: Optional[GroundGrid] = None, **kw):
-        self = super().__new__(cls, *fields, **kw)
-        self.objects = objects
-        self.points = points
-        self.object_metrics = object_metrics
-        self.normals = normals
-        self.ground = ground
-        return self
-
-    def _replace(self, **kw):
-        return _ObjectsResult(*PredictResult(*self)._replace(**kw), objects=self.objects, points=self.points,
-                              object_metrics=self.object_metrics, normals=self.normals, ground=self.ground)
-
-
-# what ``PipelinedPredictor`` hands through its slot pipeline in the place of the ground truth: the step's ground truth, its readout
-# boxes and, for the point cloud, its intrinsics (of the source frames, on the device)
-_Step = namedtuple("_Step", ["depth_gt", "boxes", "intrinsics", "size", "camera_pose"], defaults=(None, None, None))     # size: the step's final size (``resize``)
 
 Frames = Union[torch.Tensor, PlanarFrames, Sequence[Union[torch.Tensor, PlanarFrames]]]
 
@@ -109,14 +79,39 @@ def colormap_table(name: str = "inferno_r") -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(lut)).to(torch.uint8)
 
 
+def _options(keyword: str, given, keys: Tuple[str, ...], spelt: Optional[str] = None) -> dict:
+    """A copy of a predictor keyword's dict; a key outside ``keys`` is refused (``spelt``: how the text lists them, default the tuple)."""
+    opts = dict(given)
+    bad = set(opts) - set(keys)
+    if bad:
+        raise ValueError(f"{keyword}: unknown option(s) {sorted(bad)}; expected some of {spelt or keys}")
+    return opts
+
+
+def _stride_of(opts: dict) -> Tuple[int, int]:
+    """The ``stride`` option, (sy, sx) or one int, as the (sy, sx) ``hip_ops.unproject_grid`` accepts."""
+    stride = opts.get("stride", (1, 1))
+    stride = (int(stride), int(stride)) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
+    hip_ops.unproject_grid(1, 1, stride)
+    return stride
+
+
+def _pixel_filter(keyword: str, opts: dict, min_depth: float, max_depth: float, uncertainty: bool = True) -> dict:
+    """The options that say which pixels count: ``near`` / ``far`` (default the dataset's depth range) and, with ``uncertainty``,
+    ``min_confidence`` / ``max_std`` (default: no filter)."""
+    out = {"near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth))}
+    if uncertainty:
+        out.update(min_confidence=float(opts.get("min_confidence", 0.0)), max_std=float(opts.get("max_std", float("inf"))))
+    if not out["near"] <= out["far"]:
+        raise ValueError(f"{keyword}: near = {out['near']} must be <= far = {out['far']}")
+    return out
+
+
 def _readout_options(object_depth) -> Optional[dict]:
     """The ``object_depth`` keyword of both predictors: None (no readout) or a dict with some of ``quantiles`` / ``shrink``."""
     if object_depth is None:
         return None
-    opts = dict(object_depth)
-    bad = set(opts) - {"quantiles", "shrink"}
-    if bad:
-        raise ValueError(f"object_depth: unknown option(s) {sorted(bad)}; expected some of 'quantiles', 'shrink'")
+    opts = _options("object_depth", object_depth, ("quantiles", "shrink"), "'quantiles', 'shrink'")
     return {"quantiles": tuple(opts.get("quantiles", DEFAULT_QUANTILES)), "shrink": float(opts.get("shrink", 1.0))}
 
 
@@ -124,10 +119,7 @@ def _metric_options(object_metrics) -> Optional[dict]:
     """The ``object_metrics`` keyword of both predictors: None (no per-object error) or a dict with some of ``shrink`` / ``regions``."""
     if object_metrics is None:
         return None
-    opts = dict(object_metrics)
-    bad = set(opts) - {"shrink", "regions"}
-    if bad:
-        raise ValueError(f"object_metrics: unknown option(s) {sorted(bad)}; expected some of 'shrink', 'regions'")
+    opts = _options("object_metrics", object_metrics, ("shrink", "regions"), "'shrink', 'regions'")
     return {"shrink": float(opts.get("shrink", 1.0)), "regions": bool(opts.get("regions", True))}
 
 
@@ -143,22 +135,13 @@ def _cloud_options(point_cloud, min_depth: float, max_depth: float) -> Optional[
     size is known at the call), the frame's colour in every record, no pixel index, no normal per point."""
     if point_cloud is None:
         return None
-    opts = dict(point_cloud)
-    bad = set(opts) - set(_CLOUD_KEYS)
-    if bad:
-        raise ValueError(f"point_cloud: unknown option(s) {sorted(bad)}; expected some of {_CLOUD_KEYS}")
-    stride = opts.get("stride", (1, 1))
-    stride = (int(stride), int(stride)) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
-    hip_ops.unproject_grid(1, 1, stride)
+    opts = _options("point_cloud", point_cloud, _CLOUD_KEYS)
+    stride = _stride_of(opts)
     cap = opts.get("capacity")
     if cap is not None and int(cap) < 1:
         raise ValueError(f"point_cloud: capacity must be >= 1, got {cap}")
-    out = {"stride": stride, "near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth)),
-           "min_confidence": float(opts.get("min_confidence", 0.0)), "max_std": float(opts.get("max_std", float("inf"))),
-           "capacity": None if cap is None else int(cap), "colour": bool(opts.get("colour", True)), "pixel": bool(opts.get("pixel", False))}
-    if not out["near"] <= out["far"]:
-        raise ValueError(f"point_cloud: near = {out['near']} must be <= far = {out['far']}")
-    return out
+    return {"stride": stride, **_pixel_filter("point_cloud", opts, min_depth, max_depth), "capacity": None if cap is None else int(cap),
+            "colour": bool(opts.get("colour", True)), "pixel": bool(opts.get("pixel", False))}
 
 
 def _cloud_normals(point_cloud) -> bool:
@@ -174,21 +157,15 @@ def _normal_options(surface_normals, cloud_normals: bool, min_depth: float, max_
         if not cloud_normals:
             return None
         surface_normals = {}
-    opts = dict(surface_normals)
-    bad = set(opts) - set(_NORMAL_KEYS)
-    if bad:
-        raise ValueError(f"surface_normals: unknown option(s) {sorted(bad)}; expected some of {_NORMAL_KEYS}")
+    opts = _options("surface_normals", surface_normals, _NORMAL_KEYS)
     radius = opts.get("radius", DEFAULT_RADIUS)
     if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= hip_ops.NORMALS_MAX_RADIUS:
         raise ValueError(f"surface_normals: radius must be an integer in 1..{hip_ops.NORMALS_MAX_RADIUS}, got {radius}")
     out = {"radius": int(radius), "edge_ratio": float(opts.get("edge_ratio", DEFAULT_EDGE_RATIO)),
-           "near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth)),
            "picture": bool(opts.get("picture", False)), "valid": bool(opts.get("valid", False))}
     if not out["edge_ratio"] > 0.0:
         raise ValueError(f"surface_normals: edge_ratio must be > 0, got {out['edge_ratio']}")
-    if not out["near"] <= out["far"]:
-        raise ValueError(f"surface_normals: near = {out['near']} must be <= far = {out['far']}")
-    return out
+    return {**out, **_pixel_filter("surface_normals", opts, min_depth, max_depth, uncertainty=False)}
 
 
 def _ground_options(ground_grid, min_depth: float, max_depth: float) -> Optional[dict]:
@@ -198,14 +175,9 @@ def _ground_options(ground_grid, min_depth: float, max_depth: float) -> Optional
     every output.  -> the options with ``grid`` = (x0, y0, cell, GX, GY) and ``pose`` = the keyword's pose, fp32 [1, 12] on the host."""
     if ground_grid is None:
         return None
-    opts = dict(ground_grid)
-    bad = set(opts) - set(_GROUND_KEYS)
-    if bad:
-        raise ValueError(f"ground_grid: unknown option(s) {sorted(bad)}; expected some of {_GROUND_KEYS}")
+    opts = _options("ground_grid", ground_grid, _GROUND_KEYS)
     d = _GROUND_DEFAULTS
-    stride = opts.get("stride", (1, 1))
-    stride = (int(stride), int(stride)) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
-    hip_ops.unproject_grid(1, 1, stride)
+    stride = _stride_of(opts)
     band = tuple(float(v) for v in opts.get("band", d["band"]))
     limit = hip_ops.GROUND_GRID_MAX_HEIGHT
     if len(band) != 2 or not band[0] <= band[1] or not abs(band[0]) <= limit or not abs(band[1]) <= limit:
@@ -225,22 +197,175 @@ def _ground_options(ground_grid, min_depth: float, max_depth: float) -> Optional
         raise ValueError(f"ground_grid: height, pitch and roll must be finite, got {angles}")
     out = {"grid": _grid_of(opts.get("cell", d["cell"]), opts.get("x_range", d["x_range"]), opts.get("y_range", d["y_range"])),
            "pose": _ground_pose(*angles), "band": band, "obstacle_height": float(opts.get("obstacle_height", d["obstacle_height"])),
-           "stride": stride, "near": float(opts.get("near", min_depth)), "far": float(opts.get("far", max_depth)),
-           "min_confidence": float(opts.get("min_confidence", 0.0)), "max_std": float(opts.get("max_std", float("inf"))),
-           "want": tuple(n for n in hip_ops.GROUND_GRID_WANT if n in want), **counts}
+           "stride": stride, "want": tuple(n for n in hip_ops.GROUND_GRID_WANT if n in want), **counts}
     if out["obstacle_height"] != out["obstacle_height"]:
         raise ValueError("ground_grid: obstacle_height is NaN")
-    if not out["near"] <= out["far"]:
-        raise ValueError(f"ground_grid: near = {out['near']} must be <= far = {out['far']}")
-    return out
+    return {**out, **_pixel_filter("ground_grid", opts, min_depth, max_depth)}
 
 
 def _cloud_want(cloud: Optional[dict]) -> Tuple[str, ...]:
-    """The maps a point cloud's filters read beyond "depth": they are made for it (and ``bin_stats`` turned on) even when ``want``
-    leaves them out."""
+    """The maps a point cloud's (or a ground grid's) filters read beyond "depth": they are made for it (and ``bin_stats`` turned on)
+    even when ``want`` leaves them out."""
     if cloud is None:
         return ()
     return (("confidence",) if cloud["min_confidence"] > 0.0 else ()) + (("depth_std",) if cloud["max_std"] < float("inf") else ())
+
+
+def _filter_maps(maps: dict, o: dict) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(the "confidence" map, the "depth_std" map) of a step, each only if the readout's own threshold reads it."""
+    return (maps.get("confidence") if o["min_confidence"] > 0.0 else None), (maps.get("depth_std") if o["max_std"] < float("inf") else None)
+
+
+def _per_frame(ends: "_Ends", step: "_Step", device, conf: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None):
+    """What a readout that takes intrinsics needs per entry of ``step.frames`` (a list of differently sized frames has an origin -- hence a
+    principal point -- per frame): (the frames, their slice of the batch, top, left of their window, K of the slice shifted by that
+    origin -- ``point_cloud.shift_intrinsics``'s statement, the offsets cached on the device --, the slices of ``conf`` / ``std`` or None)."""
+    i = 0
+    for f in step.frames:
+        s = slice(i, i + int(f.shape[0]))
+        top, left, _, _ = _window(ends.args, int(f.shape[1]), int(f.shape[2]), ends.crop)
+        yield f, s, top, left, step.K[s] - ends._shift(device, top, left), None if conf is None else conf[s], None if std is None else std[s]
+        i = s.stop
+
+
+# The outputs behind the final map.  Each is run by one function (ends, step, made) -> its result, on the current stream; ``made`` holds
+# the step's final ``maps``, the names the caller ``asked`` for, the model's ``pred`` / ``mirror`` maps and the ground truth ``depth_gt``,
+# and under its attribute name the result of every readout that ran in front.
+def _run_errors(ends, step, made) -> ObjectMetrics:
+    """The depth error per box / region, right behind the metric launch, from the tensors that launch reads."""
+    return _object_metrics(made["pred"], made["depth_gt"], step.boxes, ends.args, pred_mirror=made["mirror"], **ends.errors)
+
+
+def _run_objects(ends, step, made) -> ObjectDepths:
+    """The per-object readout of the final map; ``std_mean`` is filled when the caller's ``want`` names "depth_std"."""
+    maps = made["maps"]
+    return object_depths(maps["depth"], step.boxes, depth_std=maps.get("depth_std") if "depth_std" in made["asked"] else None, **ends.readout)
+
+
+def _run_cloud(ends, step, made) -> PointCloud:
+    """The point cloud of a step's final map: one launch pair per entry of ``step.frames`` into one set of buffers.  With a
+    ``pixel_format`` other than rgb24 the colour is read from the window's RGB24 copy, made by one more launch in front
+    (``hip_ops.frames_to_rgb24``): bytes 12 - 14 of a record are Statement P's R, G, B.  The pixel index is made for the cloud's
+    ``normals=True`` even when ``pixel`` was not asked for; it is then left in ``made["pixel"]`` and not handed out with the cloud."""
+    c, maps = ends.cloud, made["maps"]
+    depth = maps["depth"]
+    B, _, H, W = (int(v) for v in depth.shape)
+    gh, gw = hip_ops.unproject_grid(H, W, c["stride"])
+    cap = gh * gw if c["capacity"] is None else c["capacity"]
+    dev = depth.device
+    bufs = {"points": torch.empty((B, cap, 4), dtype=torch.float32, device=dev),
+            "counts": torch.empty((B,), dtype=torch.int32, device=dev), "total": torch.empty((B,), dtype=torch.int32, device=dev)}
+    want_pixel = c["pixel"] or ends.cloud_normals
+    if want_pixel:
+        bufs["pixel"] = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    recolour = c["colour"] and ends.fmt is not None and ends.fmt.name != "rgb24"
+    # byte 15 of a record is the confidence whenever that map is made, whatever the threshold
+    for f, s, top, left, K, conf, std in _per_frame(ends, step, dev, maps.get("confidence"), _filter_maps(maps, c)[1]):
+        colour, ctop, cleft = (f if c["colour"] else None), top, left
+        if recolour:
+            colour, ctop, cleft = hip_ops.frames_to_rgb24(f, ends.fmt, top, left, (H, W)), 0, 0
+        hip_ops.depth_unproject(depth[s], K, cap, stride=c["stride"], near=c["near"], far=c["far"], confidence=conf,
+                                min_confidence=c["min_confidence"], depth_std=std, max_std=c["max_std"], frames=colour, top=ctop,
+                                left=cleft, want_pixel=want_pixel, out=bufs, image_index=s.start)
+    made["pixel"] = bufs.get("pixel")
+    return PointCloud(bufs["points"], bufs["counts"], bufs["total"], bufs.get("pixel") if c["pixel"] else None)
+
+
+def _run_normals(ends, step, made) -> SurfaceNormals:
+    """The surface normals of a step's final map (Statement N, objcavit_amd/surface_normals.py): one launch per entry of ``step.frames``
+    into one set of buffers; they read the final map only, so the frames' sizes, ``resize`` and ``pixel_format`` do not matter.  With the
+    cloud's ``normals=True`` one more launch gathers a normal per point of the cloud through its pixel index."""
+    o, depth = ends.normals, made["maps"]["depth"]
+    B, _, H, W = (int(v) for v in depth.shape)
+    dev = depth.device
+    want = ("normals",) + (("rgb8",) if o["picture"] else ()) + (("valid",) if o["valid"] else ())
+    shapes = {"normals": ((B, 3, H, W), torch.float32), "rgb8": ((B, H, W, 3), torch.uint8), "valid": ((B, H, W), torch.uint8)}
+    bufs = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
+    for _, s, _, _, K, _, _ in _per_frame(ends, step, dev):
+        hip_ops.depth_normals(depth[s], K, radius=o["radius"], near=o["near"], far=o["far"], edge_ratio=o["edge_ratio"], want=want,
+                              out=bufs, image_index=s.start)
+    points, cloud = None, made.get("points")
+    if cloud is not None and ends.cloud_normals:
+        points = hip_ops.normals_gather(bufs["normals"], made["pixel"], cloud.counts)
+    return SurfaceNormals(bufs["normals"], bufs.get("rgb8"), bufs.get("valid"), points)
+
+
+def _run_ground(ends, step, made) -> GroundGrid:
+    """The bird's-eye occupancy grid of a step's final map (Statement G, objcavit_amd/ground_grid.py): one call (three launches) per
+    entry of ``step.frames`` into one set of buffers, posed by ``step.pose`` ([B, 12], ``camera_pose=``) or, without it, by the keyword's
+    pose for every image (uploaded once per device)."""
+    o, maps = ends.ground, made["maps"]
+    depth, pose = maps["depth"], step.pose
+    B = int(depth.shape[0])
+    dev = depth.device
+    x0, y0, cell, GX, GY = o["grid"]
+    if pose is None:
+        ent = ends._on(dev, False)
+        key = ("ground_pose", B)
+        if key not in ent:
+            ent[key] = o["pose"].expand(B, 12).contiguous().to(dev)
+        pose = ent[key]
+    dtypes = {"count": torch.int32, "obstacle": torch.int32, "state": torch.uint8}
+    bufs = {n: torch.empty((B, GX) if n == "first_occupied" else (B, GY, GX), dtype=dtypes.get(n, torch.float32), device=dev)
+            for n in o["want"]}
+    for _, s, _, _, K, conf, std in _per_frame(ends, step, dev, *_filter_maps(maps, o)):
+        hip_ops.ground_grid(depth[s], K, pose[s], o["grid"], band=o["band"], obstacle_height=o["obstacle_height"],
+                            min_points=o["min_points"], min_obstacle_points=o["min_obstacle_points"], stride=o["stride"], near=o["near"],
+                            far=o["far"], confidence=conf, min_confidence=o["min_confidence"], depth_std=std, max_std=o["max_std"],
+                            want=o["want"], out=bufs, image_index=s.start)
+    return GroundGrid(*(bufs.get(n) for n in hip_ops.GROUND_GRID_WANT), x0=x0, y0=y0, cell=cell)
+
+
+# One entry per output behind the final map, IN THE ORDER OF THEIR LAUNCHES.  keyword: the predictors' keyword; attr: the attribute of the
+# result that holds the output (None when it did not run); options: the attribute of ``_Ends`` that holds the parsed keyword; parse:
+# (the predictors' readout keywords, min_depth, max_depth) -> those options or None; maps: options -> the final maps it reads, which are
+# made for it even when ``want`` leaves them out; needs: the fields of the step record it cannot run without; run: above; streamed: which
+# of its result's tensors are made on a pipeline slot's stream and read by the caller on another, so that ``submit`` must
+# ``record_stream`` them -- the per-object readout's table is NOT among them, as it never was.
+_Readout = namedtuple("_Readout", ["keyword", "attr", "options", "parse", "maps", "needs", "run", "streamed"])
+READOUTS = (
+    _Readout("object_metrics", "object_metrics", "errors", lambda kw, lo, hi: _metric_options(kw["object_metrics"]),
+             lambda o: (), ("depth_gt", "boxes"), _run_errors, slice(2)),
+    _Readout("object_depth", "objects", "readout", lambda kw, lo, hi: _readout_options(kw["object_depth"]),
+             lambda o: ("depth",), ("boxes",), _run_objects, slice(0)),
+    _Readout("point_cloud", "points", "cloud", lambda kw, lo, hi: _cloud_options(kw["point_cloud"], lo, hi),
+             lambda o: ("depth",) + _cloud_want(o), ("K",), _run_cloud, slice(None)),
+    _Readout("surface_normals", "normals", "normals",
+             lambda kw, lo, hi: _normal_options(kw["surface_normals"], _cloud_normals(kw["point_cloud"]), lo, hi),
+             lambda o: ("depth",), ("K",), _run_normals, slice(None)),
+    _Readout("ground_grid", "ground", "ground", lambda kw, lo, hi: _ground_options(kw["ground_grid"], lo, hi),
+             lambda o: ("depth",) + _cloud_want(o), ("K",), _run_ground, slice(None)),
+)
+for _r in READOUTS:
+    setattr(PredictResult, _r.attr, None)          # an ATTRIBUTE, not a field: ``PredictResult``'s fields are what they were
+
+
+class _ObjectsResult(PredictResult):
+    """A ``PredictResult`` -- same fields, same tuple -- whose attributes named in ``READOUTS`` (``objects`` / ``points`` /
+    ``object_metrics`` / ``normals`` / ``ground``) hold the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` /
+    ``SurfaceNormals`` / ``GroundGrid``; each is a keyword of its own and survives ``_replace``."""
+
+    def __new__(cls, *fields, **kw):
+        made = {r.attr: kw.pop(r.attr, None) for r in READOUTS}
+        self = super().__new__(cls, *fields, **kw)
+        self.__dict__.update(made)
+        return self
+
+    def _replace(self, **kw):
+        return _ObjectsResult(*PredictResult(*self)._replace(**kw), **{r.attr: getattr(self, r.attr) for r in READOUTS})
+
+
+class _Step(namedtuple("_Step", ["depth_gt", "boxes", "K", "frames", "pose", "size"])):
+    """The inputs of one step beside the forward's (``_Ends.step``): the ground truth as the caller gave it, the boxes as (xywh, counts),
+    the intrinsics of the source frames [B, 4] and the camera poses [B, 12] on the device (each None when absent or when no keyword
+    reads it), the frame batches and the step's final size.  ``PipelinedPredictor`` hands it through its slot pipeline in the place
+    of the ground truth."""
+    __slots__ = ()
+
+    def held(self) -> List[torch.Tensor]:
+        """The tensors among them that a pipeline slot's launches read (the frames' own are held with the ingest's)."""
+        gt = [self.depth_gt] if isinstance(self.depth_gt, torch.Tensor) else list(self.depth_gt or [])
+        return gt + list(self.boxes or ()) + [t for t in (self.K, self.pose) if t is not None]
 
 
 def _window(args, Hs: int, Ws: int, crop) -> Tuple[int, int, int, int]:
@@ -345,18 +470,20 @@ def _tensors_of(frames: list) -> List[torch.Tensor]:
 class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
-    def __init__(self, args, flip_tta: bool, loss: bool, colormap, vmin, vmax, u16_scale, crop, object_depth=None, point_cloud=None,
-                 object_metrics=None, resize=None, pixel_format=None, surface_normals=None, ground_grid=None):
+    def __init__(self, args, *, flip_tta: bool = True, loss: bool = False, colormap=None, vmin=None, vmax=None, u16_scale=None, crop=None,
+                 resize=None, pixel_format=None, **readouts):
+        """The predictors' keywords, by keyword; ``readouts``: those named in ``READOUTS``."""
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.fmt = None if pixel_format is None else PixelFormat.of(pixel_format)      # None: rgb24 through the rgb24 calls
         self.resize = _model_size(resize)
-        self.readout = _readout_options(object_depth)
-        self.errors = _metric_options(object_metrics)
         self.min_depth, self.max_depth = _depth_range(args)
-        self.cloud = _cloud_options(point_cloud, self.min_depth, self.max_depth)
-        self.cloud_normals = _cloud_normals(point_cloud)          # a normal per point of the cloud
-        self.normals = _normal_options(surface_normals, self.cloud_normals, self.min_depth, self.max_depth)
-        self.ground = _ground_options(ground_grid, self.min_depth, self.max_depth)
+        given = {r.keyword: readouts.pop(r.keyword, None) for r in READOUTS}
+        if readouts:
+            raise TypeError(f"_Ends: unknown keyword(s) {sorted(readouts)}")
+        for r in READOUTS:                           # .errors, .readout, .cloud, .normals, .ground: the parsed keyword or None
+            setattr(self, r.options, r.parse(given, self.min_depth, self.max_depth))
+        self.cloud_normals = _cloud_normals(given["point_cloud"])          # a normal per point of the cloud
+        self.readouts = tuple((r, r.maps(getattr(self, r.options))) for r in READOUTS if getattr(self, r.options) is not None)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -410,13 +537,13 @@ class _Ends:
         return hip_ops.frame_yuv_tables(frames[0].device, self.fmt)
 
     def ingest(self, frames: list, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``.  With ``resize``
-        every frame's window is resized to the model's size by that launch (``hip_ops.frame_resize_ingest``); with ``pixel_format``
-        the frames are read in that format by the same launch (``hip_ops.frame_ingest_format`` / ``frame_resize_ingest_format``)."""
+        """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``
+        (``hip_ops.frame_window_ingest``).  With ``resize`` every frame's window is resized to the model's size by that launch; with
+        ``pixel_format`` the frames are read in that format by the same launch."""
         for f in frames:
             if f.device.type != "cuda":
                 raise HipLibraryError(f"frames are on {f.device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
-        Hw, Ww = self.window_of(frames)
+        window = self.window_of(frames)
         H, W = self.model_size(frames)
         taps = self.taps_of(frames)
         B = sum(int(f.shape[0]) for f in frames)
@@ -428,16 +555,8 @@ class _Ends:
         i = 0
         for f in frames:
             top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            if self.fmt is not None:
-                if taps is None:
-                    hip_ops.frame_ingest_format(f, table, self.fmt, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
-                else:
-                    hip_ops.frame_resize_ingest_format(f, table, (H, W), self.fmt, top, left, (Hw, Ww), mirror_too=self.flip_tta, out=out,
-                                                       out_index=i, taps=taps)
-            elif taps is None:
-                hip_ops.frame_ingest(f, table, top, left, (H, W), mirror_too=self.flip_tta, out=out, out_index=i)
-            else:
-                hip_ops.frame_resize_ingest(f, table, (H, W), top, left, (Hw, Ww), mirror_too=self.flip_tta, out=out, out_index=i, taps=taps)
+            hip_ops.frame_window_ingest(f, table, top, left, window, self.resize, self.fmt, mirror_too=self.flip_tta, out=out, out_index=i,
+                                        taps=taps)
             i += int(f.shape[0])
         return out
 
@@ -496,38 +615,6 @@ class _Ends:
             raise ValueError(f"camera_pose: one row-major 3 x 4 [R | t] per frame ([{B}, 12]), got {tuple(camera_pose.shape)}")
         return camera_pose.to(device=device, dtype=torch.float32).contiguous()
 
-    def ground_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor], pose: Optional[torch.Tensor] = None) -> GroundGrid:
-        """The bird's-eye occupancy grid of a step's final map (Statement G, objcavit_amd/ground_grid.py): one call (three launches) per
-        entry of ``frames`` into one set of buffers, K shifted by each frame's window origin exactly as ``_cloud_of`` shifts it.
-        ``pose``: the step's [B, 12] (``camera_pose=``); None: the keyword's pose for every image (uploaded once per device)."""
-        o, depth = self.ground, maps["depth"]
-        B = int(depth.shape[0])
-        dev = depth.device
-        x0, y0, cell, GX, GY = o["grid"]
-        if pose is None:
-            ent = self._on(dev, False)
-            key = ("ground_pose", B)
-            if key not in ent:
-                ent[key] = o["pose"].expand(B, 12).contiguous().to(dev)
-            pose = ent[key]
-        dtypes = {"count": torch.int32, "obstacle": torch.int32, "state": torch.uint8}
-        bufs = {n: torch.empty((B, GX) if n == "first_occupied" else (B, GY, GX), dtype=dtypes.get(n, torch.float32), device=dev)
-                for n in o["want"]}
-        conf = maps.get("confidence") if o["min_confidence"] > 0.0 else None
-        std = maps.get("depth_std") if o["max_std"] < float("inf") else None
-        i = 0
-        for f in frames:
-            n = int(f.shape[0])
-            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            hip_ops.ground_grid(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), pose[i:i + n], o["grid"], band=o["band"],
-                                obstacle_height=o["obstacle_height"], min_points=o["min_points"],
-                                min_obstacle_points=o["min_obstacle_points"], stride=o["stride"], near=o["near"], far=o["far"],
-                                confidence=None if conf is None else conf[i:i + n], min_confidence=o["min_confidence"],
-                                depth_std=None if std is None else std[i:i + n], max_std=o["max_std"], want=o["want"], out=bufs,
-                                image_index=i)
-            i += n
-        return GroundGrid(*(bufs.get(n) for n in hip_ops.GROUND_GRID_WANT), x0=x0, y0=y0, cell=cell)
-
     def _shift(self, device, top: int, left: int) -> torch.Tensor:
         ent = self._on(device, False)
         key = ("shift", top, left)
@@ -535,118 +622,47 @@ class _Ends:
             ent[key] = torch.tensor([0.0, 0.0, float(left), float(top)], dtype=torch.float32, device=device)
         return ent[key]
 
-    def points_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor]) -> PointCloud:
-        """The point cloud of a step's final map (``_cloud_of``'s, as the caller asked for it)."""
-        return self._cloud_of(maps, K, frames)[0]
+    def step(self, frames: list, size: Optional[Tuple[int, int]] = None, depth_gt=None, boxes=None, intrinsics=None, camera_pose=None) -> _Step:
+        """The step record of a call's keywords: boxes padded, intrinsics and poses uploaded, on the current stream.  ``size``: the
+        frames' window size where the caller has it already."""
+        B, dev = sum(int(f.shape[0]) for f in frames), frames[0].device
+        return _Step(depth_gt, self.boxes_on(boxes, dev, B), self.intrinsics_on(intrinsics, dev, B), frames,
+                     self.pose_on(camera_pose, dev, B), size or self.window_of(frames))
 
-    def _cloud_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor]) -> Tuple[PointCloud, Optional[torch.Tensor]]:
-        """(the point cloud, its pixel index -- made for the cloud's ``normals=True`` even when ``pixel`` was not asked for, and then not
-        handed out with the cloud).  The point cloud of a step's final map: one launch pair per entry of ``frames`` (a list of differently sized frames has an
-        origin -- hence a principal point -- and a colour source per frame) into one set of buffers.  K is shifted by each frame's
-        window origin (``point_cloud.shift_intrinsics``'s statement, the offsets cached on the device).  With a ``pixel_format`` other
-        than rgb24 the colour is read from the window's RGB24 copy, made by one more launch in front (``hip_ops.frames_to_rgb24``):
-        bytes 12 - 14 of a record are Statement P's R, G, B."""
-        c, depth = self.cloud, maps["depth"]
-        B, _, H, W = (int(v) for v in depth.shape)
-        gh, gw = hip_ops.unproject_grid(H, W, c["stride"])
-        cap = gh * gw if c["capacity"] is None else c["capacity"]
-        dev = depth.device
-        bufs = {"points": torch.empty((B, cap, 4), dtype=torch.float32, device=dev),
-                "counts": torch.empty((B,), dtype=torch.int32, device=dev), "total": torch.empty((B,), dtype=torch.int32, device=dev)}
-        want_pixel = c["pixel"] or self.cloud_normals
-        if want_pixel:
-            bufs["pixel"] = torch.empty((B, cap), dtype=torch.int32, device=dev)
-        conf = maps.get("confidence")
-        std = maps.get("depth_std") if c["max_std"] < float("inf") else None
-        i = 0
-        for f in frames:
-            n = int(f.shape[0])
-            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            colour, ctop, cleft = (f if c["colour"] else None), top, left
-            if colour is not None and self.fmt is not None and self.fmt.name != "rgb24":
-                colour, ctop, cleft = hip_ops.frames_to_rgb24(f, self.fmt, top, left, (H, W)), 0, 0
-            hip_ops.depth_unproject(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), cap, stride=c["stride"], near=c["near"],
-                                    far=c["far"], confidence=None if conf is None else conf[i:i + n], min_confidence=c["min_confidence"],
-                                    depth_std=None if std is None else std[i:i + n], max_std=c["max_std"],
-                                    frames=colour, top=ctop, left=cleft, want_pixel=want_pixel, out=bufs, image_index=i)
-            i += n
-        return PointCloud(bufs["points"], bufs["counts"], bufs["total"], bufs.get("pixel") if c["pixel"] else None), bufs.get("pixel")
-
-    def normals_of(self, maps: dict, K: torch.Tensor, frames: List[torch.Tensor], cloud: Optional[PointCloud] = None,
-                   pixel: Optional[torch.Tensor] = None) -> SurfaceNormals:
-        """The surface normals of a step's final map (Statement N, objcavit_amd/surface_normals.py): one launch per entry of ``frames``
-        into one set of buffers, K shifted by each frame's window origin exactly as ``points_of`` shifts it; they read the final map only,
-        so the frames' sizes, ``resize`` and ``pixel_format`` do not matter.  With the cloud's ``normals=True`` one more launch gathers a
-        normal per point of ``cloud`` through its ``pixel`` index."""
-        o, depth = self.normals, maps["depth"]
-        B, _, H, W = (int(v) for v in depth.shape)
-        dev = depth.device
-        want = ("normals",) + (("rgb8",) if o["picture"] else ()) + (("valid",) if o["valid"] else ())
-        shapes = {"normals": ((B, 3, H, W), torch.float32), "rgb8": ((B, H, W, 3), torch.uint8), "valid": ((B, H, W), torch.uint8)}
-        bufs = {n: torch.empty(shapes[n][0], dtype=shapes[n][1], device=dev) for n in want}
-        i = 0
-        for f in frames:
-            n = int(f.shape[0])
-            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            hip_ops.depth_normals(depth[i:i + n], K[i:i + n] - self._shift(dev, top, left), radius=o["radius"], near=o["near"], far=o["far"],
-                                  edge_ratio=o["edge_ratio"], want=want, out=bufs, image_index=i)
-            i += n
-        points = None
-        if cloud is not None and pixel is not None:
-            points = hip_ops.normals_gather(bufs["normals"], pixel, cloud.counts)
-        return SurfaceNormals(bufs["normals"], bufs.get("rgb8"), bufs.get("valid"), points)
-
-    def finish(self, out, mirror, size: Tuple[int, int], depth_gt: Optional[torch.Tensor], first_image_id: int,
-               want: Tuple[str, ...], boxes=None, cloud=None, camera_pose=None) -> PredictResult:
+    def finish(self, out, mirror, step: _Step, first_image_id: int, want: Tuple[str, ...]) -> PredictResult:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
-        the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  ``boxes``
-        (``boxes_on``'s pair): with the ``object_depth`` keyword the per-object readout right behind the final map, which is then made
-        even if ``want`` leaves it out; with the ``object_metrics`` keyword and ground truth the per-object error right behind the metric
-        launch, from the tensors that launch reads.
-        ``cloud`` = (K of the source frames [B, 4], the frames): with the ``point_cloud`` keyword the point cloud behind the map (and behind
-        the readout), with the maps its filters read made likewise; with the ``surface_normals`` keyword (or the cloud's ``normals=True``)
-        the normals behind the cloud; with the ``ground_grid`` keyword the occupancy grid behind them, posed by ``camera_pose`` (fp32
-        [B, 12] on the device) or, without it, by the keyword's pose."""
+        the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  Behind them
+        every readout of ``READOUTS`` whose keyword is set and whose ``needs`` the step has, in that order: the per-object error right
+        behind the metric launch, the object readout, the point cloud, the normals, the occupancy grid.  The maps they read are made
+        even when ``want`` leaves them out (and are then not handed out)."""
         asked = want
-        errors = boxes if (self.errors is not None and depth_gt is not None) else None
-        boxes = boxes if self.readout is not None else None
-        if (boxes is not None or cloud is not None) and "depth" not in want:
-            want = want + ("depth",)
-        if cloud is not None:
-            want = want + tuple(w for w in _cloud_want(self.cloud) if w not in want)
-            want = want + tuple(w for w in _cloud_want(self.ground) if w not in want)
+        live = [r for r, _ in self.readouts if None not in [getattr(step, n) for n in r.needs]]
+        for r, reads in self.readouts:
+            want = want + tuple(w for w in reads if r in live and w not in want)
         pred = out.depth_pred.contiguous()
         mirror_pred = None if mirror is None else mirror.depth_pred.contiguous()
+        depth_gt = self.ground_truth(step.depth_gt, int(pred.shape[0]))
         edges = getattr(out, "bin_edges", None)
         maps = {}
         if want:
             cmap = self._on(pred.device, True)["cmap"] if "rgb8" in want else None
             stats = [getattr(o, k, None) if _need_stats(want) else None for o in (out, mirror) for k in ("depth_var", "confidence")]
             stats = [None if t is None else t.contiguous() for t in stats]
-            maps = hip_ops.depth_finalize(pred, self.min_depth, self.max_depth, size, pred_mirror=mirror_pred, want=want,
+            maps = hip_ops.depth_finalize(pred, self.min_depth, self.max_depth, step.size, pred_mirror=mirror_pred, want=want,
                                           u16_scale=self.u16_scale, colormap=cmap, vmin=self.vmin, vmax=self.vmax,
                                           var=stats[0], pmax=stats[1], var_mirror=stats[2], pmax_mirror=stats[3])
         rec = None
         if depth_gt is not None:
             rec = _records(pred, mirror_pred, edges, depth_gt, self.args, self.min_depth, self.max_depth, first_image_id, self.loss)
-        table = None if errors is None else _object_metrics(pred, depth_gt, errors, self.args, pred_mirror=mirror_pred, **self.errors)
         res = PredictResult(maps.get("depth") if "depth" in asked else None, maps.get("depth_u16"), maps.get("rgb8"), rec, edges,
                             maps.get("depth_std") if "depth_std" in asked else None,
                             maps.get("confidence") if "confidence" in asked else None)
-        if boxes is None and cloud is None and table is None:
+        if not live:
             return res
-        objects = None
-        if boxes is not None:
-            objects = object_depths(maps["depth"], boxes, depth_std=maps.get("depth_std") if "depth_std" in asked else None, **self.readout)
-        points = pixel = normals = None
-        if cloud is not None and self.cloud is not None:
-            points, pixel = self._cloud_of(maps, *cloud)
-        if cloud is not None and self.normals is not None:
-            normals = self.normals_of(maps, *cloud, cloud=points, pixel=pixel if self.cloud_normals else None)
-        ground = None
-        if cloud is not None and self.ground is not None:
-            ground = self.ground_of(maps, *cloud, pose=camera_pose)
-        return _ObjectsResult(*res, objects=objects, points=points, object_metrics=table, normals=normals, ground=ground)
+        made = {"maps": maps, "asked": asked, "pred": pred, "mirror": mirror_pred, "depth_gt": depth_gt}
+        for r in live:
+            made[r.attr] = r.run(self, step, made)
+        return _ObjectsResult(*res, **{r.attr: made[r.attr] for r in live})
 
 
 def _need_stats(want) -> bool:
@@ -747,8 +763,9 @@ class Predictor:
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
-                          pixel_format, surface_normals, ground_grid)
+        self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
+                          resize=resize, pixel_format=pixel_format, object_depth=object_depth, point_cloud=point_cloud,
+                          object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -767,13 +784,9 @@ class Predictor:
         if _need_stats(want) or (intrinsics is not None and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground))):
             _turn_stats_on(self.model)
         frames = self.ends.frames_of(frames_u8, "frames_u8")
-        B = sum(int(f.shape[0]) for f in frames)
-        size = self.ends.window_of(frames)
-        out, mirror = self._forward(frames, B)
-        K = self.ends.intrinsics_on(intrinsics, frames[0].device, B)
-        return self.ends.finish(out, mirror, size, self.ends.ground_truth(depth_gt, B), first_image_id, want,
-                                self.ends.boxes_on(boxes, frames[0].device, B), None if K is None else (K, frames),
-                                self.ends.pose_on(camera_pose, frames[0].device, B))
+        out, mirror = self._forward(frames, sum(int(f.shape[0]) for f in frames))
+        step = self.ends.step(frames, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose)
+        return self.ends.finish(out, mirror, step, first_image_id, want)
 
 
 class PipelinedPredictor(_SlotPipeline):
@@ -812,8 +825,9 @@ class PipelinedPredictor(_SlotPipeline):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
-        self.ends = _Ends(args, flip_tta, loss, colormap, vmin, vmax, u16_scale, crop, object_depth, point_cloud, object_metrics, resize,
-                          pixel_format, surface_normals, ground_grid)
+        self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
+                          resize=resize, pixel_format=pixel_format, object_depth=object_depth, point_cloud=point_cloud,
+                          object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
@@ -832,10 +846,8 @@ class PipelinedPredictor(_SlotPipeline):
         return self.ends.ingest(frames)                      # the slot's static input has long been overwritten: ingest again
 
     def _finish(self, out, step: _Step, first_image_id: int) -> PredictResult:
-        gt = self.ends.ground_truth(step.depth_gt, self.B)
         out, mirror = _split(out, self.B) if self.flip_tta else (out, None)
-        res = self.ends.finish(out, mirror, step.size or self.size, gt, first_image_id, self.want, step.boxes, step.intrinsics,
-                               step.camera_pose)
+        res = self.ends.finish(out, mirror, step, first_image_id, self.want)
         return res._replace(bin_edges=res.bin_edges.clone() if (self.want_edges and res.bin_edges is not None) else None)
 
     def collect(self) -> List[PredictResult]:
@@ -859,21 +871,14 @@ class PipelinedPredictor(_SlotPipeline):
         # ``pixel_format``: likewise the tables of Statement P; every plane of a ``PlanarFrames`` is held like the frames
         taps = self.ends.taps_of(frames)
         yuv = self.ends.yuv_of(frames)
-        held = list(taps or ()) + ([] if yuv is None else [yuv]) + _tensors_of(frames)
-        held += [depth_gt] if isinstance(depth_gt, torch.Tensor) else list(depth_gt or [])
-        boxes = self.ends.boxes_on(boxes, frames[0].device, self.B)
-        held += list(boxes or ())
-        K = self.ends.intrinsics_on(intrinsics, frames[0].device, self.B)
-        held += [] if K is None else [K]
-        pose = self.ends.pose_on(camera_pose, frames[0].device, self.B)
-        held += [] if pose is None else [pose]
-        self._submit(frames, held, _Step(depth_gt, boxes, None if K is None else (K, frames), size, pose), first_image_id,
-                     (object_features, object_xywh_list))
+        step = self.ends.step(frames, size, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose)
+        held = list(taps or ()) + ([] if yuv is None else [yuv]) + _tensors_of(frames) + step.held()
+        self._submit(frames, held, step, first_image_id, (object_features, object_xywh_list))
         made = self._pending[-1].result
-        for t in (tuple(getattr(made, "points", None) or ()) + tuple((getattr(made, "object_metrics", None) or ())[:2]) +
-                  tuple(getattr(made, "normals", None) or ()) + tuple(getattr(made, "ground", None) or ())):
-            if isinstance(t, torch.Tensor):                                # made on the slot's stream, read by the caller on this one
-                t.record_stream(torch.cuda.current_stream(t.device))
+        for r, _ in self.ends.readouts:                                    # ``READOUTS.streamed``: made on the slot's stream, read by
+            for t in tuple(getattr(made, r.attr) or ())[r.streamed]:       # the caller on this one
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(torch.cuda.current_stream(t.device))
 
     def records(self, results: Sequence[PredictResult]) -> torch.Tensor:
         """The record table [N * B, 10] ([N * B, 16] with ``loss``) of collected results that carried ground truth."""

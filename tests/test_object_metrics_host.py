@@ -194,7 +194,7 @@ def test_predict_keyword_is_parsed_and_the_pins_hold():
     # the boxes are handed through with either keyword, and with neither they are not
     dev = torch.device("cpu")
     boxes = [torch.tensor([[5.0, 5.0, 2.0, 2.0]])]
-    ends = lambda **kw: _Ends(args, True, False, None, None, None, None, None, **kw)      # noqa: E731
+    ends = lambda **kw: _Ends(args, flip_tta=True, loss=False, **kw)      # noqa: E731
     assert ends().boxes_on(boxes, dev, 1) is None and ends(object_metrics={}).boxes_on(None, dev, 1) is None
     for kw in (dict(object_metrics={}), dict(object_depth={}), dict(object_metrics={}, object_depth={})):
         xywh, counts = ends(**kw).boxes_on(boxes, dev, 1)
