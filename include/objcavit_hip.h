@@ -767,6 +767,37 @@ int ocv_frame_resize_ingest_format(int format, const uint8_t* plane0, long frame
 int ocv_frames_to_rgb24(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1, long frame_stride1,
                         long row_stride1, const uint8_t* plane2, long frame_stride2, long row_stride2, const int* yuv_table, int Hs, int Ws,
                         int top, int left, uint8_t* out, int B, int Hw, int Ww, ocv_stream_t stream);
+/* Lens on ingest: the rectified Hw x Ww window of DISTORTED frames of any format, as ocv_frame_ingest_format / ocv_frames_to_rgb24 write
+ * a cropped one.  The geometry is the host's: a map of the source coordinate of every rectified pixel, made in float64
+ * (objcavit_amd/lens.py: any model -- rational Brown-Conrady, Kannala-Brandt fisheye, coordinates exported from elsewhere) and quantised
+ * to fixed point.  The device applies STATEMENT L, in integers only:
+ *   map   int32 [M][Hw][Ww][2] in device memory, M = 1 (one camera for the batch) or M = B (a map per image), 16-byte aligned.  Entry
+ *         (X, Y) of rectified pixel (u, v) is its source coordinate in units of 1/256 pixel, relative to the WHOLE source frame (pixel
+ *         centres at integer indices): X = floor(xs * 256 + 0.5) in float64, clamped by the host to [-256, Ws * 256] (Y: [-256,
+ *         Hs * 256]), NaN -> -256.  The device needs no range check beyond the tap test below and is safe for any int32.
+ *   taps  x0 = X >> 8 (arithmetic), wx = X & 255; y0, wy likewise; (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1).  A tap
+ *         outside 0 <= x < Ws, 0 <= y < Hs has R = G = B = 0 (a constant black border, decided per tap); a tap inside is the R, G, B of
+ *         that source pixel in the frames' format -- for NV12 / I420 Statement P applied per tap, chroma sample (x >> 1, y >> 1).
+ *   byte  acc = (256 - wx)(256 - wy) v00 + wx (256 - wy) v10 + (256 - wx) wy v01 + wx wy v11 per channel;
+ *         byte = (acc + 32768) >> 16   (acc + 32768 <= 255 * 65536 + 32768: int32 holds it, no clamp).
+ * ocv_frame_remap_ingest_fwd: table[c][byte] at (b, c, v, u) of out fp32 [B][3][Hw][Ww] and, with mirror_too, at (b, c, v, Ww - 1 - u) of
+ *   the image mirror_offset elements behind -- the layout, out / mirror_offset rules and 16-byte / scalar store rule of
+ *   ocv_frame_ingest_fwd (16-byte stores: Ww % 4 == 0, out 16-byte aligned, mirror_offset % 4 == 0).
+ * ocv_frames_remap_rgb24_fwd: the three bytes at out uint8 [B][Hw][Ww][3], every byte written.
+ * Consequences: the first is bit-equal to ocv_frame_ingest_fwd of the second's output; an identity map (X = 256 (left + u),
+ * Y = 256 (top + v)) is bit-equal to ocv_frame_ingest_fwd / ocv_frame_ingest_format at (top, left).
+ * The plane arguments are those of ocv_frame_ingest_format.  -1 before any launch, the message naming the entry point: its source checks
+ * (null plane, unknown format, bad sizes, strides, yuv_table), null map / table / out, Hw or Ww < 1, a map that is not 16-byte
+ * aligned, M outside {1, B}, misaligned out / table, a mirrored half that overlaps the batch.  One launch each, no workspace, no
+ * synchronisation, no atomics (hipGraph-capturable; two calls give identical bytes). */
+int ocv_frame_remap_ingest_fwd(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1,
+                               long frame_stride1, long row_stride1, const uint8_t* plane2, long frame_stride2, long row_stride2,
+                               const int* yuv_table, int Hs, int Ws, const int* map, int M, int Hw, int Ww, const float* table, float* out,
+                               int B, int mirror_too, long mirror_offset, ocv_stream_t stream);
+int ocv_frames_remap_rgb24_fwd(int format, const uint8_t* plane0, long frame_stride0, long row_stride0, const uint8_t* plane1,
+                               long frame_stride1, long row_stride1, const uint8_t* plane2, long frame_stride2, long row_stride2,
+                               const int* yuv_table, int Hs, int Ws, const int* map, int M, int Hw, int Ww, uint8_t* out, int B,
+                               ocv_stream_t stream);
 /* Predict path, output end(modules/GraphBinsLM.py:159-183,295-301,367, metrics/MetricsPreprocess.py:17-24): the map the metric pass
  * above forms per pixel, written out.  pred [B][1][h][w], pred_mirror nullable and still mirrored (as for the metric pass):
  *   d = resize_{H x W, bilinear, align_corners}(0.5 (clamp(pred) + clamp(flip(pred_mirror)))  or  clamp(pred)), nan -> min_depth,

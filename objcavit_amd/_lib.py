@@ -136,6 +136,11 @@ PROTOTYPES = {
                                         C.c_int, C.c_long, _stream]),
     "ocv_frames_to_rgb24": (C.c_int, [C.c_int] + [_u8p, C.c_long, C.c_long] * 3 + [C.c_void_p] + [C.c_int] * 4 + [_u8p, C.c_int, C.c_int,
                                       C.c_int, _stream]),
+    # lens on ingest (Statement L): the source of ocv_frame_ingest_format, the int32 map [M][Hw][Ww][2], M, the window's Hw, Ww
+    "ocv_frame_remap_ingest_fwd": (C.c_int, [C.c_int] + [_u8p, C.c_long, C.c_long] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_long, _stream]),
+    "ocv_frames_remap_rgb24_fwd": (C.c_int, [C.c_int] + [_u8p, C.c_long, C.c_long] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int, _u8p, C.c_int, _stream]),
     "ocv_depth_finalize_fwd": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, C.c_void_p, C.c_float,
                                          _u8p, _u8p, C.c_float, C.c_float, C.c_int, _stream]),
     "ocv_depth_finalize_stats_fwd": (C.c_int, [_f32p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_int,

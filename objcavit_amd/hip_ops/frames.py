@@ -1,5 +1,5 @@
 """hip_ops frames: the two ends of the predict path -- decoded uint8 / uint16 frames in (csrc/frame_ingest.hip; a window of any size
-resized to the model's on the way in: csrc/frame_resize.hip), full-resolution depth maps out (csrc/depth_finalize.hip).  What is read
+resized to the model's on the way in: csrc/frame_resize.hip; the rectified window of distorted frames: csrc/frame_remap.hip), full-resolution depth maps out (csrc/depth_finalize.hip).  What is read
 out of the final map behind them is ``readouts``.  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, one launch on the current stream, ``out=`` writes straight into a buffer the caller owns (a captured graph's
 static input).  The four ingest wrappers are fronts of one function, ``_ingest``."""
@@ -11,6 +11,7 @@ import torch
 
 from .. import _lib
 from .._lib import check
+from ..lens import LensMap
 from ..pixel_formats import PixelFormat, PlanarFrames, plane_strides
 from ._core import _ptr, _req, _stream, timed
 
@@ -311,6 +312,79 @@ def frames_to_rgb24(frames, pixel_format, top: int = 0, left: int = 0, size: Opt
     return out
 
 
+def _lens_on(lens_map, device, B: int, Hs: int, Ws: int, who: str) -> torch.Tensor:
+    """The device map of a ``lens.LensMap`` (uploaded when first used on ``device``, then kept), or an int32 device tensor [M, Hw, Ww, 2]
+    of Statement L's entries as it is; M = 1 or B, and a ``LensMap``'s source size must be the frames'."""
+    if isinstance(lens_map, LensMap):
+        if lens_map.source_size != (Hs, Ws):
+            raise ValueError(f"{who}: the lens map was made for {lens_map.source_size[0]} x {lens_map.source_size[1]} frames, got {Hs} x {Ws}")
+        m = lens_map.on(device)
+    else:
+        m = lens_map
+        _req(m, f"{who}: lens_map", torch.int32)
+        if m.dim() != 4 or m.shape[3] != 2 or min(m.shape[:3]) < 1:
+            raise ValueError(f"{who}: lens_map must be a LensMap or int32 [M, Hw, Ww, 2], got {tuple(m.shape)}")
+    if int(m.shape[0]) not in (1, B):
+        raise ValueError(f"{who}: {int(m.shape[0])} maps for {B} frame(s): one map for the batch or one per frame")
+    return m
+
+
+def frame_remap_ingest(frames, table: torch.Tensor, lens_map, pixel_format=None, mirror_too: bool = False,
+                       out: Optional[torch.Tensor] = None, out_index: int = 0, yuv_tables: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``frame_ingest_format`` through a lens: the rectified window of DISTORTED frames of any ``pixel_format`` (None: rgb24; frames as
+    ``frame_ingest_format`` takes them) -> fp32 NCHW [B, 3, Hw, Ww], every channel value the ``table`` entry of the byte Statement L
+    (include/objcavit_hip.h, ``objcavit_amd.lens``) gathers for the pixel: four taps of the source frame in the format's own fetch,
+    8-bit weights, integer arithmetic, a black border.  ``lens_map``: a ``LensMap`` made for the frames' size (its device copy is
+    uploaded on the current stream when first used, then kept) or an int32 device tensor [M, Hw, Ww, 2], M = 1 or B.  ``mirror_too``,
+    ``out``, ``out_index``: as ``frame_ingest`` takes them.  One launch (ocv_frame_remap_ingest_fwd) on the current stream; bit-equal to
+    ``frame_ingest`` of ``frames_remap_rgb24``'s bytes, and with ``LensMap.identity`` to ``frame_ingest_format`` of that window."""
+    lib = _lib.load()
+    who = "frame_remap_ingest"
+    fmt = PixelFormat.of(pixel_format)
+    B, Hs, Ws, device, planes = _source(frames, fmt, who)
+    m = _lens_on(lens_map, device, B, Hs, Ws, who)
+    Hw, Ww = int(m.shape[1]), int(m.shape[2])
+    _req(table, "table")
+    if tuple(table.shape) != (3, 256):
+        raise ValueError(f"{who}: table must be [3, 256], got {tuple(table.shape)}")
+    if out is None:
+        out = torch.empty((2 * B if mirror_too else B, 3, Hw, Ww), dtype=torch.float32, device=device)
+        out_index = 0
+    else:
+        _req(out, f"{who}: out")
+        if out.dim() != 4 or tuple(out.shape[1:]) != (3, Hw, Ww):
+            raise ValueError(f"{who}: out must be [N, 3, {Hw}, {Ww}], got {tuple(out.shape)}")
+    N = int(out.shape[0])
+    half = N // 2 if mirror_too else N
+    if (mirror_too and N % 2) or out_index < 0 or out_index + B > half:
+        raise ValueError(f"{who}: {B} image(s) at index {out_index} do not fit out {tuple(out.shape)}"
+                         f"{' (first half: the second takes the mirrors)' if mirror_too else ''}")
+    plane = 3 * Hw * Ww
+    with timed(who):
+        check(lib.ocv_frame_remap_ingest_fwd(fmt.id, *planes, _ptr(_yuv_on(device, fmt, yuv_tables)), Hs, Ws, m.data_ptr(), int(m.shape[0]),
+                                             Hw, Ww, table.data_ptr(), out.data_ptr() + 4 * plane * int(out_index), B,
+                                             1 if mirror_too else 0, half * plane, _stream()), "ocv_frame_remap_ingest_fwd")
+    return out
+
+
+def frames_remap_rgb24(frames, lens_map, pixel_format=None, out: Optional[torch.Tensor] = None,
+                       yuv_tables: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rectified window of distorted frames (as ``frame_remap_ingest`` takes them, through the same ``lens_map``) -> packed RGB uint8
+    [B, Hw, Ww, 3]: the bytes of Statement L themselves.  ``out``: a contiguous uint8 [B, Hw, Ww, 3] to write.  One launch
+    (ocv_frames_remap_rgb24_fwd) on the current stream, every output byte written."""
+    lib = _lib.load()
+    who = "frames_remap_rgb24"
+    fmt = PixelFormat.of(pixel_format)
+    B, Hs, Ws, device, planes = _source(frames, fmt, who)
+    m = _lens_on(lens_map, device, B, Hs, Ws, who)
+    Hw, Ww = int(m.shape[1]), int(m.shape[2])
+    out = _out_slice(out, (B, Hw, Ww, 3), torch.uint8, device, who)
+    with timed(who):
+        check(lib.ocv_frames_remap_rgb24_fwd(fmt.id, *planes, _ptr(_yuv_on(device, fmt, yuv_tables)), Hs, Ws, m.data_ptr(), int(m.shape[0]),
+                                             Hw, Ww, out.data_ptr(), B, _stream()), "ocv_frames_remap_rgb24_fwd")
+    return out
+
+
 def depth_ingest(depth_u16: torch.Tensor, factor: float, top: int = 0, left: int = 0, size: Optional[Tuple[int, int]] = None,
                  out: Optional[torch.Tensor] = None, out_index: int = 0) -> torch.Tensor:
     """uint16 ground-truth depth [B, Hs, Ws] (as in the 16-bit PNGs) -> fp32 metres [B, 1, H, W] = float(v) / ``factor`` over the same
@@ -423,5 +497,6 @@ def depth_finalize(pred: torch.Tensor, min_depth: float, max_depth: float, size:
 
 
 __all__ = ["frame_ingest", "frame_ingest_format", "frame_resize_ingest_format", "frame_window_ingest", "frames_to_rgb24", "frame_yuv_tables",
+           "frame_remap_ingest", "frames_remap_rgb24",
            "resize_taps", "frame_resize_supported", "frame_resize_taps", "frame_resize_ingest", "FRAME_RESIZE_MAX_RATIO", "depth_ingest",
            "depth_finalize", "colormap_scale"]

@@ -21,6 +21,7 @@ import torch
 
 from . import hip_ops
 from ._lib import HipLibraryError
+from .lens import LensMap
 from .object_depth import DEFAULT_QUANTILES, ObjectDepths, object_depths, pad_boxes
 from .object_metrics import ObjectMetrics, object_metrics as _object_metrics
 from .pixel_formats import PixelFormat, PlanarFrames
@@ -223,7 +224,7 @@ def _per_frame(ends: "_Ends", step: "_Step", device, conf: Optional[torch.Tensor
     i = 0
     for f in step.frames:
         s = slice(i, i + int(f.shape[0]))
-        top, left, _, _ = _window(ends.args, int(f.shape[1]), int(f.shape[2]), ends.crop)
+        top, left = ends.origin_of(f)
         yield f, s, top, left, step.K[s] - ends._shift(device, top, left), None if conf is None else conf[s], None if std is None else std[s]
         i = s.stop
 
@@ -258,12 +259,14 @@ def _run_cloud(ends, step, made) -> PointCloud:
     want_pixel = c["pixel"] or ends.cloud_normals
     if want_pixel:
         bufs["pixel"] = torch.empty((B, cap), dtype=torch.int32, device=dev)
-    recolour = c["colour"] and ends.fmt is not None and ends.fmt.name != "rgb24"
+    recolour = c["colour"] and (ends.lens is not None or (ends.fmt is not None and ends.fmt.name != "rgb24"))
+    n = 0
     # byte 15 of a record is the confidence whenever that map is made, whatever the threshold
     for f, s, top, left, K, conf, std in _per_frame(ends, step, dev, maps.get("confidence"), _filter_maps(maps, c)[1]):
         colour, ctop, cleft = (f if c["colour"] else None), top, left
         if recolour:
-            colour, ctop, cleft = hip_ops.frames_to_rgb24(f, ends.fmt, top, left, (H, W)), 0, 0
+            colour, ctop, cleft = ends.rgb24_of(step.frames, n, top, left, (H, W)), 0, 0
+        n += 1
         hip_ops.depth_unproject(depth[s], K, cap, stride=c["stride"], near=c["near"], far=c["far"], confidence=conf,
                                 min_confidence=c["min_confidence"], depth_std=std, max_std=c["max_std"], frames=colour, top=ctop,
                                 left=cleft, want_pixel=want_pixel, out=bufs, image_index=s.start)
@@ -471,11 +474,17 @@ class _Ends:
     """What both predictors share: the device tables and the two ends around a forward."""
 
     def __init__(self, args, *, flip_tta: bool = True, loss: bool = False, colormap=None, vmin=None, vmax=None, u16_scale=None, crop=None,
-                 resize=None, pixel_format=None, **readouts):
+                 resize=None, pixel_format=None, lens=None, **readouts):
         """The predictors' keywords, by keyword; ``readouts``: those named in ``READOUTS``."""
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.fmt = None if pixel_format is None else PixelFormat.of(pixel_format)      # None: rgb24 through the rgb24 calls
         self.resize = _model_size(resize)
+        if lens is not None and not isinstance(lens, LensMap):
+            raise TypeError(f"lens: expected a LensMap (objcavit_amd.lens), got {type(lens).__name__}")
+        if lens is not None and crop is not None:
+            raise ValueError("lens: the map's window is the window -- crop= cannot be given beside lens= (build the map for the window wanted)")
+        self.lens = lens
+        self._rect = (None, None)                    # (the frame list last ingested through the lens with ``resize``, its RGB24 copies)
         self.min_depth, self.max_depth = _depth_range(args)
         given = {r.keyword: readouts.pop(r.keyword, None) for r in READOUTS}
         if readouts:
@@ -503,7 +512,19 @@ class _Ends:
             ent["cmap"] = cm.to(device=device, dtype=torch.uint8).contiguous()
         return ent
 
+    def origin_of(self, f) -> Tuple[int, int]:
+        """(top, left) of a frame batch's window in the pixels its intrinsics are given in: under ``lens`` the rectified window itself."""
+        if self.lens is not None:
+            return 0, 0
+        return _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)[:2]
+
     def window_of(self, frames: List[torch.Tensor]) -> Tuple[int, int]:
+        if self.lens is not None:
+            for f in frames:
+                if (int(f.shape[1]), int(f.shape[2])) != self.lens.source_size:
+                    raise ValueError(f"lens: the map was made for {self.lens.source_size[0]} x {self.lens.source_size[1]} frames, got "
+                                     f"{int(f.shape[1])} x {int(f.shape[2])}")
+            return self.lens.window_size
         sizes = {_window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)[2:] for f in frames}
         if len(sizes) != 1:
             raise ValueError(f"frames of one batch must crop to one size, got {sorted(sizes)}")
@@ -536,10 +557,31 @@ class _Ends:
             raise HipLibraryError(f"frames are on {frames[0].device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
         return hip_ops.frame_yuv_tables(frames[0].device, self.fmt)
 
+    def lens_of(self, frames: list) -> Optional[torch.Tensor]:
+        """With ``lens``: the map on the frames' device, uploaded on the current stream when first used there and kept for good."""
+        if self.lens is None:
+            return None
+        if frames[0].device.type != "cuda":
+            raise HipLibraryError(f"frames are on {frames[0].device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
+        return self.lens.on(frames[0].device)
+
+    def rgb24_of(self, frames: list, n: int, top: int, left: int, size: Tuple[int, int]) -> torch.Tensor:
+        """The window of entry ``n`` of a step's ``frames`` as packed RGB24 (the point cloud's colour): ``hip_ops.frames_to_rgb24``; under
+        ``lens`` the rectified window -- the copy the ingest made when it went through ``resize``, else one ``frames_remap_rgb24`` launch."""
+        if self.lens is None:
+            return hip_ops.frames_to_rgb24(frames[n], self.fmt, top, left, size)
+        if self._rect[0] is frames:
+            return self._rect[1][n]
+        return hip_ops.frames_remap_rgb24(frames[n], self.lens, self.fmt)
+
     def ingest(self, frames: list, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> [batch | mirrored batch] (or the batch alone without TTA) fp32 NCHW: one launch per entry of ``frames``
         (``hip_ops.frame_window_ingest``).  With ``resize`` every frame's window is resized to the model's size by that launch; with
-        ``pixel_format`` the frames are read in that format by the same launch."""
+        ``pixel_format`` the frames are read in that format by the same launch.  With ``lens`` the launch is
+        ``hip_ops.frame_remap_ingest`` (the rectified window, any format); ``lens`` and ``resize`` together take TWO launches per entry:
+        ``hip_ops.frames_remap_rgb24``, then ``frame_resize_ingest`` of its output -- that RGB24 copy is kept for the step's readouts."""
+        if self.lens is not None:
+            self.window_of(frames)                   # a frame of another size than the map's is refused before anything else
         for f in frames:
             if f.device.type != "cuda":
                 raise HipLibraryError(f"frames are on {f.device}: the predict path runs only on a ROCm GPU (there is no CPU fallback)")
@@ -553,11 +595,20 @@ class _Ends:
         elif int(out.shape[0]) != (2 * B if self.flip_tta else B):
             raise ValueError(f"{B} frame(s) do not fill a batch of {tuple(out.shape)}")
         i = 0
+        rect = []
         for f in frames:
-            top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
-            hip_ops.frame_window_ingest(f, table, top, left, window, self.resize, self.fmt, mirror_too=self.flip_tta, out=out, out_index=i,
-                                        taps=taps)
+            if self.lens is None:
+                top, left, _, _ = _window(self.args, int(f.shape[1]), int(f.shape[2]), self.crop)
+                hip_ops.frame_window_ingest(f, table, top, left, window, self.resize, self.fmt, mirror_too=self.flip_tta, out=out,
+                                            out_index=i, taps=taps)
+            elif self.resize is None:
+                hip_ops.frame_remap_ingest(f, table, self.lens, self.fmt, mirror_too=self.flip_tta, out=out, out_index=i)
+            else:
+                rect.append(hip_ops.frames_remap_rgb24(f, self.lens, self.fmt))
+                hip_ops.frame_window_ingest(rect[-1], table, 0, 0, window, self.resize, None, mirror_too=self.flip_tta, out=out,
+                                            out_index=i, taps=taps)
             i += int(f.shape[0])
+        self._rect = (frames, rect) if rect else (None, None)
         return out
 
     def ground_truth(self, depth_gt, B: int) -> Optional[torch.Tensor]:
@@ -568,6 +619,9 @@ class _Ends:
             if depth_gt.dim() != 4 or depth_gt.shape[0] != B or depth_gt.shape[1] != 1:
                 raise ValueError(f"depth_gt: expected fp32 [{B}, 1, H, W] or uint16 frames, got {tuple(depth_gt.shape)}")
             return depth_gt.contiguous()
+        if self.lens is not None:
+            raise ValueError("depth_gt: under lens= the ground truth is fp32 [B, 1, Hw, Ww] in the rectified window; uint16 frames are "
+                             "refused because depth cannot be interpolated across the lens map (rectify the ground truth beforehand)")
         maps = _frame_list(depth_gt, "depth_gt", 3)
         H, W = self.window_of(maps)
         if sum(int(m.shape[0]) for m in maps) != B:
@@ -594,13 +648,26 @@ class _Ends:
         """The intrinsics of a step -- a [B, 4] tensor or a list of per-frame 4-vectors, fx, fy, cx, cy in pixels of the SOURCE frames --
         as fp32 [B, 4] on the device, or None without intrinsics / with none of the ``point_cloud``, ``surface_normals`` and
         ``ground_grid`` keywords."""
-        if (self.cloud is None and self.normals is None and self.ground is None) or intrinsics is None:
+        if self.cloud is None and self.normals is None and self.ground is None:
             return None
+        if intrinsics is None:
+            if not self.has_default_K:
+                return None
+            ent = self._on(device, False)                                          # the rectified window's own camera, for every frame
+            key = ("lens_K", B)
+            if key not in ent:
+                ent[key] = torch.tensor(self.lens.new_K, dtype=torch.float32).expand(B, 4).contiguous().to(device)
+            return ent[key]
         if not isinstance(intrinsics, torch.Tensor):
             intrinsics = torch.stack([torch.as_tensor(k, dtype=torch.float32).reshape(-1).cpu() for k in intrinsics], 0)
         if tuple(intrinsics.shape) != (B, 4):
             raise ValueError(f"intrinsics: one (fx, fy, cx, cy) per frame ([{B}, 4]), got {tuple(intrinsics.shape)}")
         return intrinsics.to(device=device, dtype=torch.float32).contiguous()
+
+    @property
+    def has_default_K(self) -> bool:
+        """Whether a call without ``intrinsics=`` still has a camera: the ``lens`` map's ``new_K``."""
+        return self.lens is not None and self.lens.new_K is not None
 
     def pose_on(self, camera_pose, device, B: int) -> Optional[torch.Tensor]:
         """The camera poses of a step -- a [B, 12] (or [B, 3, 4]) tensor or a list of per-frame 3 x 4 [R | t], camera frame to ground
@@ -719,6 +786,16 @@ class Predictor:
     Statement P (integer, tables by the host for the format's ``matrix`` and ``range``; chroma replicated) INSIDE the ingest launch, with
     or without ``resize``.  Everything behind the ingest is unchanged; the point cloud's colour is read from the window's RGB24 copy
     (``hip_ops.frames_to_rgb24``, one more launch).
+    ``lens``: None, or a ``LensMap`` (objcavit_amd/lens.py: ``LensMap.brown`` / ``fisheye`` / ``from_coordinates``) -- the frames are
+    DISTORTED frames of the map's source size (else ``ValueError``), in any ``pixel_format``, and the ingest launch gathers the map's
+    rectified window out of them (Statement L, csrc/frame_remap.hip: bilinear, integer, black border) straight into the model's
+    input.  The map's window is the window: ``crop=`` is refused, the window origin is (0, 0), every output has the window's size, and
+    ``boxes=`` / fp32 ground truth ([B, 1, Hw, Ww]) are in pixels of the rectified window; uint16 ground-truth frames are refused
+    (depth cannot be interpolated).  ``intrinsics=`` is in pixels of the rectified window and DEFAULTS to ``lens.new_K``: the readouts
+    that need a camera then run without the keyword.  With ``resize`` the ingest takes two launches per frame batch
+    (``hip_ops.frames_remap_rgb24``, then ``frame_resize_ingest`` of its output); the point cloud's colour reads the rectified RGB24
+    copy -- that one, or without ``resize`` one more ``frames_remap_rgb24`` launch.  ``lens.valid`` tells which pixels have all four taps
+    inside the frame; nothing masks by it.
     ``object_depth``: None, or a dict with some of ``quantiles`` / ``shrink`` -- the per-object readout (objcavit_amd/object_depth.py).
     With it, ``boxes=`` of a call -- the boxes a detector found in the B frames, in pixels of the cropped window: a list of [N_i, >= 4]
     tensors / None, an (xywh, counts) pair or a ``PaddedObjects``; independent of the objects the model's provider is fed -- is read out
@@ -759,12 +836,12 @@ class Predictor:
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
-                 ground_grid: Optional[dict] = None, pixel_format=None,
+                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
-                          resize=resize, pixel_format=pixel_format, object_depth=object_depth, point_cloud=point_cloud,
+                          resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
                           object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid)
         self.flip_tta = flip_tta
 
@@ -781,7 +858,7 @@ class Predictor:
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",),
                  camera_pose=None, intrinsics=None, boxes=None) -> PredictResult:
         want = _check_want(want)
-        if _need_stats(want) or (intrinsics is not None and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground))):
+        if _need_stats(want) or ((intrinsics is not None or self.ends.has_default_K) and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground))):
             _turn_stats_on(self.model)
         frames = self.ends.frames_of(frames_u8, "frames_u8")
         out, mirror = self._forward(frames, sum(int(f.shape[0]) for f in frames))
@@ -807,6 +884,8 @@ class PipelinedPredictor(_SlotPipeline):
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
     ``pixel_format``: as ``Predictor``'s; every plane of a submitted ``PlanarFrames`` is held like the frames, the tables of Statement P
     are uploaded on the caller's stream when first used, a re-run step is ingested again from its kept planes.
+    ``lens``: as ``Predictor``'s; the map's device copy is made once and outlives every step, the RGB24 copy of a ``resize`` step is
+    made on the slot's stream and kept with the step.
 
         pp = PipelinedPredictor(model, args, example_frames, want=("depth_u16",))
         for i, frame in enumerate(frames):                    # uint8 [1, Hs, Ws, 3] on the device
@@ -819,14 +898,14 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
-                 ground_grid: Optional[dict] = None, pixel_format=None,
+                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
         self.want_edges = "bin_edges" in tuple(want)
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
-                          resize=resize, pixel_format=pixel_format, object_depth=object_depth, point_cloud=point_cloud,
+                          resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
                           object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
@@ -871,6 +950,7 @@ class PipelinedPredictor(_SlotPipeline):
         # ``pixel_format``: likewise the tables of Statement P; every plane of a ``PlanarFrames`` is held like the frames
         taps = self.ends.taps_of(frames)
         yuv = self.ends.yuv_of(frames)
+        self.ends.lens_of(frames)                    # ``lens``: the map's device copy is made HERE when the device is new; it is kept for good
         step = self.ends.step(frames, size, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose)
         held = list(taps or ()) + ([] if yuv is None else [yuv]) + _tensors_of(frames) + step.held()
         self._submit(frames, held, step, first_image_id, (object_features, object_xywh_list))
