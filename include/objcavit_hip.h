@@ -44,7 +44,8 @@ typedef void* ocv_stream_t;
  * later ADDED (still 5: a new symbol changes nothing for an existing caller) ocv_conv3x3_nhwc_strided_fwd (EfficientNetV2),
  * ocv_depth_metrics_loss_workspace_bytes / ocv_depth_metrics_loss_fwd (validation loss),
  * ocv_depth_normals_fwd / ocv_normals_gather_fwd (surface normals of the final map, Statement N),
- * ocv_ground_grid_workspace_bytes / ocv_ground_grid_fwd (bird's-eye occupancy grid of the final map, Statement G);
+ * ocv_ground_grid_workspace_bytes / ocv_ground_grid_fwd (bird's-eye occupancy grid of the final map, Statement G),
+ * ocv_ground_plane_workspace_bytes / ocv_ground_plane_fwd (ground plane of the final map, Statement E);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -950,6 +951,66 @@ int ocv_ground_grid_fwd(const float* depth, const float* K, const float* pose, c
                         int GX, int GY, float lo, float hi, float obstacle_height, int min_points, int min_obstacle_points, int* count,
                         int* obstacle, float* h_min, float* h_max, float* h_mean, uint8_t* state, float* first_occupied, void* workspace,
                         size_t workspace_bytes, ocv_stream_t stream);
+/* Ground plane of the final map, STATEMENT E (no counterpart in the reference; the statement the tests compare against is
+ * tests/ground_plane_ref.py: fp32 torch on the CPU with one eager op per rounding, the solve in float64 one operation at a time.  The
+ * counts, the moments and the stats match it EXACTLY; the pose within one fp32 step, equal bits expected).  It estimates, per image, the
+ * camera's pose over the ground -- the [R | t] ocv_ground_grid_fwd takes -- from the map itself: a consensus over a FIXED table of
+ * hypotheses (RANSAC whose table is made on the host, so nothing is random at run time), then ONE refit from integer moments.
+ * INPUTS  depth fp32 [B][1][H][W];  K fp32 [B][4] in DEVICE memory, 16-byte aligned;  confidence / depth_std (nullable) with
+ * min_confidence / max_std, the stride sy, sx and near <= far: the keep rule of csrc/keep_pixel.hpp, as ocv_ground_grid_fwd takes them;
+ * triples int32 [T][3] in DEVICE memory, 1 <= T <= OCV_GROUND_PLANE_MAX_HYPOTHESES: each entry a pixel index y * W + x of the map, one
+ * table for the whole batch;  prior fp32 [B][12] in DEVICE memory, 16-byte aligned: a ground-pose-style [R | t] whose row 2,
+ * u = (prior[8], prior[9], prior[10]), is the expected up direction and which is the FALLBACK output;  tol >= 0 and rel_tol >= 0, finite;
+ * h_lo <= h_hi;  cos_tilt in (0, 1];  min_cross > 0;  min_inliers >= 3.
+ * Every fp32 operation below is rounded on its own (a product that feeds a sum too), `/` and sqrtf are the IEEE ones.  Back-projection is
+ * Statement G's:  rx = (float(x) - cx) / fx,  ry = (float(y) - cy) / fy,  P = (rx * z, ry * z, z).
+ * 1. HYPOTHESES, per (b, t).  P0, P1, P2 = the points of the triple's pixels;  a = P1 - P0,  b = P2 - P0;
+ *   m = (a1 * b2 - a2 * b1,  a2 * b0 - a0 * b2,  a0 * b1 - a1 * b0);  l = sqrtf((m0 * m0 + m1 * m1) + m2 * m2);  n = m / l, negated if
+ *   n1 > 0 (the camera's y points down: up has n1 < 0);  h = -((n0 * P0x + n1 * P0y) + n2 * P0z).
+ *   VALID iff (NaN fails each comparison) all three indices lie in [0, H * W); all three pixels are kept by the keep rule with in = true
+ *   (the stride does not apply to triples; a bad camera keeps nothing);  l >= min_cross;  (n0 * u0 + n1 * u1) + n2 * u2 >= cos_tilt;
+ *   h_lo <= h <= h_hi;  the image's twelve prior values are finite.  Nothing is read through an index outside the map.
+ * 2. CONSENSUS.  The candidates are the pixels of the strided grid that the keep rule keeps: exactly ocv_ground_grid_fwd's.  For a
+ *   candidate (X, Y, Z):  thr = tol + rel_tol * Z;  count[b][t] int32 = the number of candidates with
+ *   fabsf(((n0 * X + n1 * Y) + n2 * Z) + h) <= thr;  0 for an invalid hypothesis.
+ * 3. SELECTION.  best[b] = the smallest t with the largest count; -1 if that count is below min_inliers.
+ * 4. MOMENTS (best >= 0), over the candidates that are inliers of `best` by the same test and have |X|, |Y|, |Z| <= 256:
+ *   q = (int)rintf(v * 128.f) per coordinate (|q| <= 2^15: products fit an int32), nine int64 sums in this order:
+ *   N, Sx, Sy, Sz, Sxx, Sxz, Szz, Sxy, Szy.  The entry point refuses more than 2^22 candidates per image, so every sum stays below 2^53
+ *   and converts to float64 without rounding.  All zero when best = -1.
+ * 5. SOLVE, float64, every operation rounded on its own:  mx = Sx / N, my = Sy / N, mz = Sz / N;  cxx = Sxx / N - mx * mx, likewise
+ *   cxz = Sxz / N - mx * mz, czz = Szz / N - mz * mz, cxy = Sxy / N - mx * my, czy = Szy / N - mz * my;  det = cxx * czz - cxz * cxz;
+ *   A = (cxy * czz - czy * cxz) / det;  Bc = (czy * cxx - cxy * cxz) / det;  C = ((my - A * mx) - Bc * mz) / 128;
+ *   s = sqrt((A * A + 1) + Bc * Bc);  up = (A / s, -1 / s, Bc / s);  hgt = C / s;
+ *   g = (-(up2 * up0), -(up2 * up1), 1 - up2 * up2);  lf = sqrt((g0 * g0 + g1 * g1) + g2 * g2);  f = g / lf (the optical axis projected
+ *   onto the plane: forward);  r = f x up = (f1 * up2 - f2 * up1,  f2 * up0 - f0 * up2,  f0 * up1 - f1 * up0) (right).
+ *   ok = 1 iff best >= 0, N >= min_inliers, det > 0, h_lo <= hgt <= h_hi, (up0 * u0 + up1 * u1) + up2 * u2 >= cos_tilt (all in float64,
+ *   the fp32 arguments converted), and -- so that the output is never NaN unless the prior is -- lf > 0 and the twelve values below are
+ *   finite as fp32.
+ * 6. OUTPUTS, EVERY element written.  pose fp32 [B][12] = [r, 0; f, 0; up, hgt], each rounded once to fp32, where ok; the twelve prior
+ *   values bit for bit elsewhere.  Row 2 is the plane; rows 0 and 1 follow ground_pose's convention (objcavit_amd/ground_grid.py), so on a
+ *   perfect plane the output equals ground_pose(h, pitch, roll).  stats int32 [B][4] = best, count[best] (0 if none), N, ok.
+ * workspace: ocv_ground_plane_workspace_bytes(B, T) bytes (0 for sizes the entry point refuses), 16-byte aligned, EVERY byte written.
+ *   With Tp = T rounded up to a multiple of OCV_GROUND_PLANE_BATCH:  fp32 [B][Tp][4] the hypotheses n0, n1, n2, h (an invalid or padding one is 0, 0, 0, NaN)
+ *   at byte 0;  int64 [B][9] the moments at byte 16 * B * Tp;  int32 [B][T] the counts at byte 16 * B * Tp + 72 * B.
+ * Four launches on the stream (csrc/ground_plane.hip): hypotheses (which also clears counts and moments);  consensus, one 256-thread
+ * workgroup per (image, tile of OCV_GROUND_PLANE_TILE consecutive candidates of the strided grid), candidates in registers, a wave-uniform
+ * loop over the hypotheses, a ballot popcount per test, counts gathered in LDS, one global integer add per (workgroup, hypothesis with a
+ * non-zero count);  moments, the same tiling, which finds `best` from the T counts itself and issues nine 64-bit integer adds per
+ * workgroup;  solve, one wave per image.  INTEGER atomics only: two calls give identical bytes.  No allocation, no synchronisation, nothing
+ * read on the host (capturable).  Images are independent: a batch can be filled by one call per image with offset pointers.
+ * -1 with a message before any launch on: a null depth / K / triples / prior / pose / stats / workspace, non-positive sizes, T outside
+ * 1..1024, H * W or B * tiles at or above 2^31, more than 2^22 candidates per image, a stride below 1, near > far, tol or rel_tol negative
+ * or infinite, h_lo > h_hi, cos_tilt outside (0, 1], min_cross <= 0 (or a NaN in any of these), min_inliers below 3, K / prior not 16-byte
+ * aligned, the workspace not 16-byte aligned, another pointer not 4-byte aligned, a workspace that is too small. */
+#define OCV_GROUND_PLANE_TILE 1024
+#define OCV_GROUND_PLANE_MAX_HYPOTHESES 1024
+#define OCV_GROUND_PLANE_BATCH 8 /* hypotheses per uniform load of the consensus loop: the workspace pads T to a multiple of it */
+size_t ocv_ground_plane_workspace_bytes(int B, int T);
+int ocv_ground_plane_fwd(const float* depth, const float* K, const int* triples, const float* prior, const float* confidence,
+                         const float* depth_std, int B, int H, int W, int T, int sy, int sx, float near, float far, float min_confidence,
+                         float max_std, float tol, float rel_tol, float h_lo, float h_hi, float cos_tilt, float min_cross, int min_inliers,
+                         float* pose, int* stats, void* workspace, size_t workspace_bytes, ocv_stream_t stream);
 /* Depth ERROR per detection box, and over objects against background: the validation metrics of ocv_depth_metrics_fwd, segmented by the
  * boxes of ocv_object_depth_fwd (no counterpart in the reference; the statement the tests compare against is tests/object_metrics_ref.py).
  * pred, pred_mirror (nullable, still mirrored), h, w, gt, H, W, min_depth, max_depth and the crop box: exactly as ocv_depth_metrics_fwd

@@ -24,24 +24,15 @@
 // height sum a 64-bit integer add of rint(1024 h) (exact: a power-of-two product).  Integer sums and extremes do not depend on the
 // order of arrival, so two calls give identical bytes.  No allocation, no synchronisation, nothing read on the host: capturable.
 // The keep rule is the point cloud's (keep_pixel.hpp).  Every per-point operation is fp32 and rounded on its own (__fmul_rn & co., and
-// gg_mul below where a product feeds a sum: the library is built with contraction on); `/` is the IEEE division.
+// gg_mul of rounded_mul.hpp where a product feeds a sum: the library is built with contraction on); `/` is the IEEE division.
 #include "common.hpp"
 #include "keep_pixel.hpp"
+#include "rounded_mul.hpp"
 #include "../../include/objcavit_hip.h"
 
 #include <math.h>
 
 namespace {
-
-// A product rounded ON ITS OWN even where it feeds a sum.  The library is built with -ffp-contract=fast, under which the backend fuses
-// any product with the sum it feeds, whatever the source says (__fmul_rn(a, b) is `a * b` to the compiler, a contraction pragma is not
-// consulted): one rounding where Statement G has two.  The empty asm makes the product a value the compiler cannot look through; it
-// emits no instruction.
-__device__ __forceinline__ float gg_mul(float a, float b) {
-  float v = __fmul_rn(a, b);
-  asm("" : "+v"(v));
-  return v;
-}
 
 constexpr int GG_THREADS = 256, GG_ROUNDS = 4, GG_TILE = GG_THREADS * GG_ROUNDS;
 constexpr int GG_LOG_SLOTS = 10, GG_SLOTS = 1 << GG_LOG_SLOTS, GG_PROBES = 8;

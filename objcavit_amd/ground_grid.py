@@ -20,7 +20,9 @@ z forward) goes to the GROUND frame g = R P + t: g_0 lateral (right), g_1 forwar
 [R | t].  Everything per point is fp32 with every operation rounded on its own, everything per cell integer arithmetic (integer atomics
 on chip and in memory), so the grid is the same bits on every call and equal to the statement (Statement G of include/objcavit_hip.h,
 tests/ground_grid_ref.py), not merely close to it.  Cells between the camera and the first hit stay "unknown" unless they are seen: there
-is no ray casting, no fusion over time, and the pose is the caller's (an IMU's, a calibration's), not estimated from the map.
+is no ray casting, no fusion over time, and the pose is the caller's (an IMU's, a calibration's), not estimated from the map -- unless the
+predictors' ``ground_plane=`` keyword estimates it in the same step and ``ground_grid=dict(pose="plane")`` reads it
+(objcavit_amd/ground_plane.py).
 """
 from __future__ import annotations
 

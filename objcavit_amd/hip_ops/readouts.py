@@ -1,8 +1,9 @@
 """hip_ops readouts: what is read out of the predict path's final map (``frames.depth_finalize``) behind it -- per-box statistics
 (csrc/object_depth.hip), the point cloud (csrc/point_cloud.hip), the surface normals (csrc/surface_normals.hip), the bird's-eye occupancy
-grid (csrc/ground_grid.hip) and, against ground truth, the depth error per box and per region (csrc/object_metrics.hip).  Same rules as
-every wrapper: operands are checked on the host, CPU tensors raise ``HipLibraryError``, launches on the current stream, ``out=`` writes
-straight into buffers the caller owns.  The checks the wrappers share are the four helpers in front of them."""
+grid (csrc/ground_grid.hip), the ground plane that poses it (csrc/ground_plane.hip) and, against ground truth, the depth error per box
+and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
+``HipLibraryError``, launches on the current stream, ``out=`` writes straight into buffers the caller owns.  The checks the wrappers
+share are the four helpers in front of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -351,6 +352,105 @@ def ground_grid(depth: torch.Tensor, K: torch.Tensor, pose: torch.Tensor, grid: 
                                       workspace.data_ptr(), int(workspace.numel()), _stream()), "ocv_ground_grid_fwd")
     return res
 
-__all__ = ["object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics", "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
+
+GROUND_PLANE_WANT = ("pose", "stats", "count", "moments")
+GROUND_PLANE_TILE = 1024              # include/objcavit_hip.h: OCV_GROUND_PLANE_TILE, candidates of the strided grid per workgroup
+GROUND_PLANE_MAX_HYPOTHESES = 1024    # OCV_GROUND_PLANE_MAX_HYPOTHESES
+GROUND_PLANE_BATCH = 8                # OCV_GROUND_PLANE_BATCH: the workspace pads the hypotheses to a multiple of it
+GROUND_PLANE_MAX_CANDIDATES = 1 << 22  # Statement E: candidates per image (every moment then converts to float64 without rounding)
+GROUND_PLANE_MOMENTS = ("N", "Sx", "Sy", "Sz", "Sxx", "Sxz", "Szz", "Sxy", "Szy")
+
+
+def ground_plane(depth: torch.Tensor, K: torch.Tensor, triples: torch.Tensor, prior: torch.Tensor, tol: float = 0.05, rel_tol: float = 0.01,
+                 height_range: Tuple[float, float] = (0.5, 4.0), cos_tilt: float = math.cos(0.35), min_cross: float = 1e-3,
+                 min_inliers: int = 64, stride: Tuple[int, int] = (1, 1), near: float = 0.0, far: float = float("inf"),
+                 confidence: Optional[torch.Tensor] = None, min_confidence: float = 0.0, depth_std: Optional[torch.Tensor] = None,
+                 max_std: float = float("inf"), want: Tuple[str, ...] = ("pose", "stats"), out: Optional[dict] = None,
+                 workspace: Optional[torch.Tensor] = None, image_index: int = 0) -> dict:
+    """The ground plane of the final map as a camera pose (Statement E of include/objcavit_hip.h): ``depth`` fp32 [B, 1, H, W], ``K`` fp32
+    [B, 4] on the device as ``ground_grid`` takes it, ``triples`` int32 [T, 3] on the device (1 <= T <= 1024 pixel triples y * W + x, one
+    table for the batch: ``objcavit_amd.ground_plane.plane_triples``), ``prior`` fp32 [B, 12] on the device = a ``ground_pose``-style
+    [R | t] whose row 2 is the expected up direction and which is the fallback output.  Every triple whose pixels are kept (``near`` /
+    ``far``, ``confidence`` / ``depth_std`` with their thresholds, a usable camera; not the stride) spans a plane (n, h); it is a valid
+    hypothesis if the triple is not degenerate (``min_cross``), n is within ``cos_tilt`` of the prior's up and h within ``height_range``.
+    Each is scored by the number of candidates -- the kept pixels of the ``stride`` grid, ``ground_grid``'s points -- within ``tol`` +
+    ``rel_tol`` * Z of it; the best one with at least ``min_inliers`` is refitted once from the integer moments of its inliers.  ->
+    {"pose": fp32 [B, 12], the refitted plane as [right, 0; forward, 0; up, height] or the prior's bytes; "stats": int32 [B, 4] = best
+    hypothesis (-1: none), its count, the refit's points, ok}, and with ``want`` naming them {"count": int32 [B, T], "moments": int64
+    [B, 9] = ``GROUND_PLANE_MOMENTS``}: VIEWS of the workspace, valid until it is used again.  Every element is written.  ``out``:
+    {"pose", "stats"} of caller-owned buffers [N, ...] with N >= image_index + B; the B images are written at ``image_index`` and the
+    dict returned holds the whole buffers.  ``workspace``: a uint8 device tensor of at least ``ocv_ground_plane_workspace_bytes``
+    (default: the stream's workspace store).  Four launches (ocv_ground_plane_fwd) on the current stream, integer atomics only (two calls
+    give the same bytes), nothing read on the host: capturable with ``out`` and a warmed-up workspace."""
+    lib = _lib.load()
+    B, H, W = _map_and_K(depth, K, "ground_plane")
+    _req(triples, "triples", torch.int32)
+    if triples.dim() != 2 or int(triples.shape[1]) != 3 or not 1 <= int(triples.shape[0]) <= GROUND_PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"ground_plane: triples must be int32 [T, 3] with 1 <= T <= {GROUND_PLANE_MAX_HYPOTHESES}, got {tuple(triples.shape)}")
+    T = int(triples.shape[0])
+    _req(prior, "prior")
+    if tuple(prior.shape) != (B, 12):
+        raise ValueError(f"ground_plane: prior must be fp32 [{B}, 12] = a row-major 3 x 4 [R | t], got {tuple(prior.shape)}")
+    _like_depth(depth, "ground_plane", confidence=confidence, depth_std=depth_std)
+    sy, sx = int(stride[0]), int(stride[1])
+    gh, gw = unproject_grid(H, W, (sy, sx))
+    if gh * gw > GROUND_PLANE_MAX_CANDIDATES:
+        raise ValueError(f"ground_plane: {gh * gw} candidates per image, at most {GROUND_PLANE_MAX_CANDIDATES} (raise the stride)")
+    if not float(near) <= float(far):
+        raise ValueError(f"ground_plane: near = {near} must be <= far = {far}")
+    tol, rel_tol, cos_tilt, min_cross = (C.c_float(float(v)).value for v in (tol, rel_tol, cos_tilt, min_cross))
+    if not 0.0 <= tol < float("inf") or not 0.0 <= rel_tol < float("inf"):
+        raise ValueError(f"ground_plane: tol and rel_tol must be >= 0 and finite, got {tol}, {rel_tol}")
+    if len(tuple(height_range)) != 2:
+        raise ValueError(f"ground_plane: height_range must be (lo, hi), got {height_range}")
+    h_lo, h_hi = (C.c_float(float(v)).value for v in height_range)
+    if not h_lo <= h_hi:
+        raise ValueError(f"ground_plane: height_range must be (lo, hi) with lo <= hi, got {tuple(height_range)}")
+    if not 0.0 < cos_tilt <= 1.0:
+        raise ValueError(f"ground_plane: cos_tilt must be in (0, 1], got {cos_tilt}")
+    if not min_cross > 0.0:
+        raise ValueError(f"ground_plane: min_cross must be > 0, got {min_cross}")
+    if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or int(min_inliers) < 3:
+        raise ValueError(f"ground_plane: min_inliers must be an integer >= 3, got {min_inliers}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(GROUND_PLANE_WANT):
+        raise ValueError(f"ground_plane: want must name some of {GROUND_PLANE_WANT} (got {want})")
+    shapes = {"pose": ((12,), torch.float32), "stats": ((4,), torch.int32)}
+    res, at = _image_buffers(out, ("pose", "stats"), shapes, B, image_index, depth.device, "ground_plane")
+    need = int(lib.ocv_ground_plane_workspace_bytes(B, T))
+    if need == 0:
+        raise ValueError(f"ground_plane: a batch of {B} with {T} hypotheses is too large")
+    if workspace is None:
+        from ._core import workspace as _workspace
+        workspace = _workspace(need, depth.device, "ground_plane")
+    else:
+        _req(workspace, "workspace", torch.uint8)
+    with timed("ground_plane"):
+        check(lib.ocv_ground_plane_fwd(depth.data_ptr(), K.data_ptr(), triples.data_ptr(), prior.data_ptr(), _ptr(confidence), _ptr(depth_std),
+                                       B, H, W, T, sy, sx, float(near), float(far), float(min_confidence), float(max_std), tol, rel_tol,
+                                       h_lo, h_hi, cos_tilt, min_cross, int(min_inliers), at["pose"], at["stats"], workspace.data_ptr(),
+                                       int(workspace.numel()), _stream()), "ocv_ground_plane_fwd")
+    res = {n: t for n, t in res.items() if n in want}
+    views = ground_plane_workspace_views(workspace, B, T)
+    res.update({n: views[n] for n in ("moments", "count") if n in want})
+    return res
+
+
+def ground_plane_workspace_views(workspace: torch.Tensor, B: int, T: int) -> dict:
+    """{"hypotheses": fp32 [B, Tp, 4], "moments": int64 [B, 9], "count": int32 [B, T]}: views of a ``ground_plane`` workspace (uint8,
+    16-byte aligned) by the layout Statement E documents in include/objcavit_hip.h -- the ONE place on the Python side that knows it;
+    Tp = T rounded up to ``GROUND_PLANE_BATCH`` (a padding hypothesis is 0, 0, 0, NaN)."""
+    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.data_ptr() % 16:
+        raise ValueError("ground_plane: the workspace must be a flat uint8 tensor that starts 16-byte aligned")
+    Tp = -(-int(T) // GROUND_PLANE_BATCH) * GROUND_PLANE_BATCH
+    a, b = 16 * B * Tp, 16 * B * Tp + 72 * B
+    if workspace.numel() < b + 4 * B * T:
+        raise ValueError(f"ground_plane: a workspace of {workspace.numel()} bytes does not hold {B} image(s) x {T} hypotheses")
+    return {"hypotheses": workspace[:a].view(torch.float32).view(B, Tp, 4), "moments": workspace[a:b].view(torch.int64).view(B, 9),
+            "count": workspace[b:b + 4 * B * T].view(torch.int32).view(B, T)}
+
+
+__all__ = ["ground_plane", "ground_plane_workspace_views", "GROUND_PLANE_BATCH", "GROUND_PLANE_WANT", "GROUND_PLANE_TILE", "GROUND_PLANE_MAX_HYPOTHESES", "GROUND_PLANE_MAX_CANDIDATES",
+           "GROUND_PLANE_MOMENTS", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics", "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
            "unproject_grid", "UNPROJECT_TILE", "depth_normals", "normals_gather", "NORMALS_WANT", "NORMALS_MAX_RADIUS",
            "ground_grid", "GROUND_GRID_WANT", "GROUND_GRID_TILE", "GROUND_GRID_MAX_HEIGHT"]

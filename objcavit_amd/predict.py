@@ -28,6 +28,7 @@ from .pixel_formats import PixelFormat, PlanarFrames
 from .point_cloud import PointCloud
 from .surface_normals import DEFAULT_EDGE_RATIO, DEFAULT_RADIUS, SurfaceNormals
 from .ground_grid import DEFAULTS as _GROUND_DEFAULTS, GroundGrid, grid_of as _grid_of, ground_pose as _ground_pose
+from .ground_plane import DEFAULTS as _PLANE_DEFAULTS, GroundPlane, cos_of_tilt as _cos_of_tilt, plane_triples as _plane_triples
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)          # modules/GraphBinsLM.py:45
@@ -127,7 +128,9 @@ def _metric_options(object_metrics) -> Optional[dict]:
 _CLOUD_KEYS = ("stride", "near", "far", "min_confidence", "max_std", "capacity", "colour", "pixel", "normals")
 _NORMAL_KEYS = ("radius", "edge_ratio", "near", "far", "picture", "valid")
 _GROUND_KEYS = ("cell", "x_range", "y_range", "height", "pitch", "roll", "band", "obstacle_height", "min_points", "min_obstacle_points",
-                "stride", "near", "far", "min_confidence", "max_std", "want")
+                "stride", "near", "far", "min_confidence", "max_std", "want", "pose")
+_PLANE_KEYS = ("hypotheses", "rows", "seed", "tol", "rel_tol", "max_tilt", "height_range", "min_cross", "min_inliers", "height", "pitch",
+               "roll", "stride", "near", "far", "min_confidence", "max_std")
 
 
 def _cloud_options(point_cloud, min_depth: float, max_depth: float) -> Optional[dict]:
@@ -169,14 +172,57 @@ def _normal_options(surface_normals, cloud_normals: bool, min_depth: float, max_
     return {**out, **_pixel_filter("surface_normals", opts, min_depth, max_depth, uncertainty=False)}
 
 
-def _ground_options(ground_grid, min_depth: float, max_depth: float) -> Optional[dict]:
+def _plane_options(ground_plane, min_depth: float, max_depth: float) -> Optional[dict]:
+    """The ``ground_plane`` keyword of both predictors: None (no estimate) or a dict with some of ``_PLANE_KEYS``.  Defaults: 256
+    hypotheses drawn with seed 0 from the map's lower half, inliers within 0.05 m + 1 % of their depth, planes within 0.35 rad of the
+    prior's up and 0.5 .. 4 m below the camera, at least 64 inliers; the prior a level camera 1.65 m above the ground; every pixel within
+    the dataset's depth range, no uncertainty filter.  -> the options with ``cos_tilt`` and ``prior`` = the prior pose, fp32 [1, 12] on
+    the host (the table of triples is made per map size, at the call)."""
+    if ground_plane is None:
+        return None
+    opts = _options("ground_plane", ground_plane, _PLANE_KEYS)
+    d = _PLANE_DEFAULTS
+    T = opts.get("hypotheses", d["hypotheses"])
+    if isinstance(T, bool) or int(T) != T or not 1 <= int(T) <= hip_ops.GROUND_PLANE_MAX_HYPOTHESES:
+        raise ValueError(f"ground_plane: hypotheses must be an integer in 1..{hip_ops.GROUND_PLANE_MAX_HYPOTHESES}, got {T}")
+    rows = opts.get("rows", d["rows"])
+    if rows is not None and (len(tuple(rows)) != 2 or not 0 <= int(rows[0]) < int(rows[1])):
+        raise ValueError(f"ground_plane: rows must be (first, end) with 0 <= first < end, got {rows}")
+    tol, rel_tol, min_cross = (float(opts.get(n, d[n])) for n in ("tol", "rel_tol", "min_cross"))
+    if not 0.0 <= tol < float("inf") or not 0.0 <= rel_tol < float("inf"):
+        raise ValueError(f"ground_plane: tol and rel_tol must be >= 0 and finite, got {tol}, {rel_tol}")
+    if not min_cross > 0.0:
+        raise ValueError(f"ground_plane: min_cross must be > 0, got {min_cross}")
+    hr = tuple(float(v) for v in opts.get("height_range", d["height_range"]))
+    if len(hr) != 2 or not hr[0] <= hr[1]:
+        raise ValueError(f"ground_plane: height_range must be (lo, hi) with lo <= hi, got {opts.get('height_range')}")
+    n = opts.get("min_inliers", d["min_inliers"])
+    if isinstance(n, bool) or int(n) != n or int(n) < 3:
+        raise ValueError(f"ground_plane: min_inliers must be an integer >= 3, got {n}")
+    angles = [float(opts.get(name, d[name])) for name in ("height", "pitch", "roll")]
+    if not all(math.isfinite(v) for v in angles):
+        raise ValueError(f"ground_plane: height, pitch and roll must be finite, got {angles}")
+    out = {"hypotheses": int(T), "rows": None if rows is None else (int(rows[0]), int(rows[1])), "seed": int(opts.get("seed", d["seed"])),
+           "tol": tol, "rel_tol": rel_tol, "cos_tilt": _cos_of_tilt(opts.get("max_tilt", d["max_tilt"])), "height_range": hr,
+           "min_cross": min_cross, "min_inliers": int(n), "prior": _ground_pose(*angles), "stride": _stride_of(opts)}
+    return {**out, **_pixel_filter("ground_plane", opts, min_depth, max_depth)}
+
+
+def _ground_options(ground_grid, min_depth: float, max_depth: float, plane: bool = False) -> Optional[dict]:
     """The ``ground_grid`` keyword of both predictors: None (no grid) or a dict with some of ``_GROUND_KEYS``.  Defaults: cells of 0.1 m
     over 20 m x 40 m in front of a level camera 1.65 m above the ground, the band -0.5 .. 2.5 m, obstacles above 0.3 m, a cell known
     from one point on and occupied from three obstacle points on; every pixel within the dataset's depth range, no uncertainty filter,
-    every output.  -> the options with ``grid`` = (x0, y0, cell, GX, GY) and ``pose`` = the keyword's pose, fp32 [1, 12] on the host."""
+    every output.  ``pose``: None (the keyword's ``height`` / ``pitch`` / ``roll``) or "plane": the pose the ``ground_plane`` keyword
+    (``plane``: whether it is given; without it "plane" is refused) estimates in the same step.  -> the options with ``grid`` = (x0, y0,
+    cell, GX, GY), ``pose`` = the keyword's pose, fp32 [1, 12] on the host, and ``pose_from`` = None or "plane"."""
     if ground_grid is None:
         return None
     opts = _options("ground_grid", ground_grid, _GROUND_KEYS)
+    pose_from = opts.get("pose")
+    if pose_from not in (None, "plane"):
+        raise ValueError(f"ground_grid: pose must be None (the keyword's height / pitch / roll) or 'plane', got {pose_from!r}")
+    if pose_from == "plane" and not plane:
+        raise ValueError("ground_grid: pose='plane' needs the ground_plane= keyword beside it (ground_plane={} takes the defaults)")
     d = _GROUND_DEFAULTS
     stride = _stride_of(opts)
     band = tuple(float(v) for v in opts.get("band", d["band"]))
@@ -198,7 +244,7 @@ def _ground_options(ground_grid, min_depth: float, max_depth: float) -> Optional
         raise ValueError(f"ground_grid: height, pitch and roll must be finite, got {angles}")
     out = {"grid": _grid_of(opts.get("cell", d["cell"]), opts.get("x_range", d["x_range"]), opts.get("y_range", d["y_range"])),
            "pose": _ground_pose(*angles), "band": band, "obstacle_height": float(opts.get("obstacle_height", d["obstacle_height"])),
-           "stride": stride, "want": tuple(n for n in hip_ops.GROUND_GRID_WANT if n in want), **counts}
+           "stride": stride, "want": tuple(n for n in hip_ops.GROUND_GRID_WANT if n in want), "pose_from": pose_from, **counts}
     if out["obstacle_height"] != out["obstacle_height"]:
         raise ValueError("ground_grid: obstacle_height is NaN")
     return {**out, **_pixel_filter("ground_grid", opts, min_depth, max_depth)}
@@ -293,15 +339,42 @@ def _run_normals(ends, step, made) -> SurfaceNormals:
     return SurfaceNormals(bufs["normals"], bufs.get("rgb8"), bufs.get("valid"), points)
 
 
+def _run_plane(ends, step, made) -> GroundPlane:
+    """The ground plane of a step's final map (Statement E, objcavit_amd/ground_plane.py): one call (four launches) per entry of
+    ``step.frames`` into one pair of buffers.  The table of triples (per map size) and the prior (per batch size) are made once per
+    device and kept."""
+    o, maps = ends.plane, made["maps"]
+    depth = maps["depth"]
+    B, _, H, W = (int(v) for v in depth.shape)
+    dev = depth.device
+    ent = ends._on(dev, False)
+    tkey, pkey = ("plane_triples", H, W), ("plane_prior", B)
+    if tkey not in ent:
+        ent[tkey] = _plane_triples(H, W, o["hypotheses"], o["rows"], o["seed"]).to(dev)
+    if pkey not in ent:
+        ent[pkey] = o["prior"].expand(B, 12).contiguous().to(dev)
+    triples, prior = ent[tkey], ent[pkey]
+    bufs = {"pose": torch.empty((B, 12), dtype=torch.float32, device=dev), "stats": torch.empty((B, 4), dtype=torch.int32, device=dev)}
+    for _, s, _, _, K, conf, std in _per_frame(ends, step, dev, *_filter_maps(maps, o)):
+        hip_ops.ground_plane(depth[s], K, triples, prior[s], tol=o["tol"], rel_tol=o["rel_tol"], height_range=o["height_range"],
+                             cos_tilt=o["cos_tilt"], min_cross=o["min_cross"], min_inliers=o["min_inliers"], stride=o["stride"],
+                             near=o["near"], far=o["far"], confidence=conf, min_confidence=o["min_confidence"], depth_std=std,
+                             max_std=o["max_std"], out=bufs, image_index=s.start)
+    return GroundPlane(bufs["pose"], bufs["stats"])
+
+
 def _run_ground(ends, step, made) -> GroundGrid:
     """The bird's-eye occupancy grid of a step's final map (Statement G, objcavit_amd/ground_grid.py): one call (three launches) per
-    entry of ``step.frames`` into one set of buffers, posed by ``step.pose`` ([B, 12], ``camera_pose=``) or, without it, by the keyword's
-    pose for every image (uploaded once per device)."""
+    entry of ``step.frames`` into one set of buffers, posed by ``step.pose`` ([B, 12], ``camera_pose=``) or, without it, by the pose the
+    ``ground_plane`` readout has just estimated (``pose="plane"``: its device tensor, read by the grid's launches behind it on the same
+    stream) or by the keyword's pose for every image (uploaded once per device)."""
     o, maps = ends.ground, made["maps"]
     depth, pose = maps["depth"], step.pose
     B = int(depth.shape[0])
     dev = depth.device
     x0, y0, cell, GX, GY = o["grid"]
+    if pose is None and o["pose_from"] == "plane":
+        pose = made["plane"].pose
     if pose is None:
         ent = ends._on(dev, False)
         key = ("ground_pose", B)
@@ -336,7 +409,9 @@ READOUTS = (
     _Readout("surface_normals", "normals", "normals",
              lambda kw, lo, hi: _normal_options(kw["surface_normals"], _cloud_normals(kw["point_cloud"]), lo, hi),
              lambda o: ("depth",), ("K",), _run_normals, slice(None)),
-    _Readout("ground_grid", "ground", "ground", lambda kw, lo, hi: _ground_options(kw["ground_grid"], lo, hi),
+    _Readout("ground_plane", "plane", "plane", lambda kw, lo, hi: _plane_options(kw["ground_plane"], lo, hi),
+             lambda o: ("depth",) + _cloud_want(o), ("K",), _run_plane, slice(None)),
+    _Readout("ground_grid", "ground", "ground", lambda kw, lo, hi: _ground_options(kw["ground_grid"], lo, hi, kw["ground_plane"] is not None),
              lambda o: ("depth",) + _cloud_want(o), ("K",), _run_ground, slice(None)),
 )
 for _r in READOUTS:
@@ -345,8 +420,8 @@ for _r in READOUTS:
 
 class _ObjectsResult(PredictResult):
     """A ``PredictResult`` -- same fields, same tuple -- whose attributes named in ``READOUTS`` (``objects`` / ``points`` /
-    ``object_metrics`` / ``normals`` / ``ground``) hold the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` /
-    ``SurfaceNormals`` / ``GroundGrid``; each is a keyword of its own and survives ``_replace``."""
+    ``object_metrics`` / ``normals`` / ``plane`` / ``ground``) hold the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` /
+    ``SurfaceNormals`` / ``GroundPlane`` / ``GroundGrid``; each is a keyword of its own and survives ``_replace``."""
 
     def __new__(cls, *fields, **kw):
         made = {r.attr: kw.pop(r.attr, None) for r in READOUTS}
@@ -489,7 +564,7 @@ class _Ends:
         given = {r.keyword: readouts.pop(r.keyword, None) for r in READOUTS}
         if readouts:
             raise TypeError(f"_Ends: unknown keyword(s) {sorted(readouts)}")
-        for r in READOUTS:                           # .errors, .readout, .cloud, .normals, .ground: the parsed keyword or None
+        for r in READOUTS:                           # .errors, .readout, .cloud, .normals, .plane, .ground: the parsed keyword or None
             setattr(self, r.options, r.parse(given, self.min_depth, self.max_depth))
         self.cloud_normals = _cloud_normals(given["point_cloud"])          # a normal per point of the cloud
         self.readouts = tuple((r, r.maps(getattr(self, r.options))) for r in READOUTS if getattr(self, r.options) is not None)
@@ -646,9 +721,9 @@ class _Ends:
 
     def intrinsics_on(self, intrinsics, device, B: int) -> Optional[torch.Tensor]:
         """The intrinsics of a step -- a [B, 4] tensor or a list of per-frame 4-vectors, fx, fy, cx, cy in pixels of the SOURCE frames --
-        as fp32 [B, 4] on the device, or None without intrinsics / with none of the ``point_cloud``, ``surface_normals`` and
-        ``ground_grid`` keywords."""
-        if self.cloud is None and self.normals is None and self.ground is None:
+        as fp32 [B, 4] on the device, or None without intrinsics / with none of the ``point_cloud``, ``surface_normals``,
+        ``ground_plane`` and ``ground_grid`` keywords."""
+        if self.cloud is None and self.normals is None and self.plane is None and self.ground is None:
             return None
         if intrinsics is None:
             if not self.has_default_K:
@@ -700,8 +775,8 @@ class _Ends:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
         the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  Behind them
         every readout of ``READOUTS`` whose keyword is set and whose ``needs`` the step has, in that order: the per-object error right
-        behind the metric launch, the object readout, the point cloud, the normals, the occupancy grid.  The maps they read are made
-        even when ``want`` leaves them out (and are then not handed out)."""
+        behind the metric launch, the object readout, the point cloud, the normals, the ground plane, the occupancy grid.  The maps they
+        read are made even when ``want`` leaves them out (and are then not handed out)."""
         asked = want
         live = [r for r, _ in self.readouts if None not in [getattr(step, n) for n in r.needs]]
         for r, reads in self.readouts:
@@ -823,11 +898,19 @@ class Predictor:
     ``pitch`` / ``roll`` (0.0, radians: ``ground_grid.ground_pose``), ``band`` ((-0.5, 2.5)), ``obstacle_height`` (0.3), ``min_points``
     (1), ``min_obstacle_points`` (3), ``stride``, ``near`` / ``far`` (default the dataset's depth range), ``min_confidence`` /
     ``max_std`` (as the cloud's: the maps are made for the filter even when ``want`` leaves them out), ``want`` (a subset of the
-    outputs) -- the bird's-eye occupancy grid of the final map (objcavit_amd/ground_grid.py, Statement G).  With it, ``intrinsics=`` of a
-    call is read by three more launches behind the finalize launch, and the result's ``ground`` ATTRIBUTE holds the ``GroundGrid`` (None
+    outputs), ``pose`` (None, or "plane": the ``ground_plane`` keyword's estimate of the same step, below) -- the bird's-eye occupancy
+    grid of the final map (objcavit_amd/ground_grid.py, Statement G).  With it, ``intrinsics=`` of a call is read by three more launches behind the finalize launch, and the result's ``ground`` ATTRIBUTE holds the ``GroundGrid`` (None
     otherwise); K is shifted by each frame's window origin as for the cloud.  ``camera_pose=`` of a call -- fp32 [B, 12] (or [B, 3, 4],
     or a list of 3 x 4), camera frame to ground frame -- replaces the keyword's pose for that call (an IMU's pose per frame).  Pass both
     by keyword.
+    ``ground_plane``: None, or a dict with some of ``hypotheses`` (256), ``rows`` ((first, end) of the map's rows the triples are drawn
+    from, default its lower half), ``seed`` (0), ``tol`` (0.05 m), ``rel_tol`` (0.01), ``max_tilt`` (0.35 rad), ``height_range``
+    ((0.5, 4.0)), ``min_cross`` (1e-3), ``min_inliers`` (64), ``height`` / ``pitch`` / ``roll`` of the prior (1.65, 0.0, 0.0),
+    ``stride``, ``near`` / ``far``, ``min_confidence`` / ``max_std`` (as the grid's) -- the camera's pose over the ground, estimated from
+    the final map (objcavit_amd/ground_plane.py, Statement E).  With it, ``intrinsics=`` of a call is read by four more launches behind
+    the normals and in front of the grid, and the result's ``plane`` ATTRIBUTE holds the ``GroundPlane`` (pose [B, 12], stats [B, 4]; None
+    otherwise); where no plane is found the pose is the prior's.  ``ground_grid=dict(pose="plane")`` makes the grid of the same step read
+    that pose on the device (refused at construction without ``ground_plane=``); ``camera_pose=`` of a call still wins.  Pass it by keyword.
     ``object_metrics``: None, or a dict with some of ``shrink`` / ``regions`` -- the depth error per box and over objects against
     background (objcavit_amd/object_metrics.py).  With it, a call that has both ``depth_gt`` and ``boxes=`` (in pixels of the ground
     truth's grid) issues one more call right behind the metric launch, on the tensors that launch reads, and the result's
@@ -836,13 +919,14 @@ class Predictor:
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
-                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, pixel_format=None,
+                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
                           resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
-                          object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid)
+                          object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid,
+                          ground_plane=ground_plane)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -858,7 +942,7 @@ class Predictor:
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",),
                  camera_pose=None, intrinsics=None, boxes=None) -> PredictResult:
         want = _check_want(want)
-        if _need_stats(want) or ((intrinsics is not None or self.ends.has_default_K) and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground))):
+        if _need_stats(want) or ((intrinsics is not None or self.ends.has_default_K) and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.plane) or _cloud_want(self.ends.ground))):
             _turn_stats_on(self.model)
         frames = self.ends.frames_of(frames_u8, "frames_u8")
         out, mirror = self._forward(frames, sum(int(f.shape[0]) for f in frames))
@@ -878,8 +962,9 @@ class PipelinedPredictor(_SlotPipeline):
     readout runs on the slot's stream, a re-run step is read out from the re-run's map.  ``point_cloud`` / ``submit(..., intrinsics=)``:
     likewise; a list of differently sized frames gives one launch pair per frame.  ``surface_normals``: as ``Predictor``'s, on the slot's
     stream behind the cloud, no host read.  ``ground_grid`` / ``submit(..., camera_pose=)``: as ``Predictor``'s, on the slot's stream behind
-    the normals; the pose is uploaded in ``submit`` and held like the frames.  ``object_metrics``: as ``Predictor``'s, on the slot's
-    stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
+    the normals; the pose is uploaded in ``submit`` and held like the frames.  ``ground_plane``: as ``Predictor``'s, on the slot's stream
+    between the normals and the grid, no host read; with ``ground_grid=dict(pose="plane")`` the grid reads the step's own estimate.
+    ``object_metrics``: as ``Predictor``'s, on the slot's stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
     graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
     ``pixel_format``: as ``Predictor``'s; every plane of a submitted ``PlanarFrames`` is held like the frames, the tables of Statement P
@@ -898,7 +983,7 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
-                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, pixel_format=None,
+                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
@@ -906,8 +991,9 @@ class PipelinedPredictor(_SlotPipeline):
         self.want = _check_want(tuple(w for w in ((want,) if isinstance(want, str) else want) if w != "bin_edges"))
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
                           resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
-                          object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid)
-        if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.ground):
+                          object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid,
+                          ground_plane=ground_plane)
+        if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.plane) or _cloud_want(self.ends.ground):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
         ex = self.ends.frames_of(example_frames, "example_frames")
