@@ -45,7 +45,8 @@ typedef void* ocv_stream_t;
  * ocv_depth_metrics_loss_workspace_bytes / ocv_depth_metrics_loss_fwd (validation loss),
  * ocv_depth_normals_fwd / ocv_normals_gather_fwd (surface normals of the final map, Statement N),
  * ocv_ground_grid_workspace_bytes / ocv_ground_grid_fwd (bird's-eye occupancy grid of the final map, Statement G),
- * ocv_ground_plane_workspace_bytes / ocv_ground_plane_fwd (ground plane of the final map, Statement E);
+ * ocv_ground_plane_workspace_bytes / ocv_ground_plane_fwd (ground plane of the final map, Statement E),
+ * ocv_obstacles_workspace_bytes / ocv_obstacles_set_dispatch / ocv_obstacles_fwd (obstacle list of the ground grid, Statement O);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -951,6 +952,54 @@ int ocv_ground_grid_fwd(const float* depth, const float* K, const float* pose, c
                         int GX, int GY, float lo, float hi, float obstacle_height, int min_points, int min_obstacle_points, int* count,
                         int* obstacle, float* h_min, float* h_max, float* h_mean, uint8_t* state, float* first_occupied, void* workspace,
                         size_t workspace_bytes, ocv_stream_t stream);
+/* Obstacle list of the ground grid, STATEMENT O (no counterpart in the reference; the statement the tests compare against is
+ * tests/obstacles_ref.py, a flood fill in numpy on the CPU: the kernel matches it EXACTLY, not within a tolerance).
+ * INPUTS, per image:  state uint8 [B][GY][GX];  nullable count, obstacle int32 [B][GY][GX] and h_max fp32 [B][GY][GX] -- the grid's
+ * outputs above, read as given;  the grid's x0, y0, cell;  link in {1, 2, 3};  min_cells >= 1;  min_obstacle_points >= 0;  cap >= 1.
+ * COMPONENTS.  A cell is occupied iff state == 2.  Two different occupied cells of one image are adjacent iff |dix| <= link and
+ * |diy| <= link (link = 1 is 8-connectivity; 2 or 3 bridges the one- or two-cell holes that a depth map's sparse far field leaves in a
+ * wall).  A component is a class of the transitive closure of adjacency; its root is its smallest iy * GX + ix.
+ * PER COMPONENT, all integer arithmetic:  n cells;  ix_min, ix_max, iy_min, iy_max;  points = the sum of count and obstacle_points = the
+ * sum of obstacle, both summed in int64 and clamped to 2^31 - 1 on output, 0 when the input is null;  sum_ix, sum_iy in int64;  h_max =
+ * the maximum of the cells' h_max through the order-preserving integer key of the grid's own extremes (csrc/float_key.hpp), 0 when the
+ * input is null.
+ * KEPT COMPONENTS.  A component is kept iff n >= min_cells and obstacle_points >= min_obstacle_points.  The kept ones are ranked by
+ * root, ascending: nearest first in forward distance, ties left to right.  total[b] = the number kept, counts[b] = min(total[b], cap).
+ * OUTPUTS, each nullable, at least one given, EVERY element of a given output written:
+ *   cells  int32 [B][cap][8] = ix_min, ix_max, iy_min, iy_max, n, points, obstacle_points, root
+ *   metres fp32  [B][cap][8] = x_min = x0 + float(ix_min) * cell,  x_max = x0 + float(ix_max + 1) * cell,  y_min, y_max likewise (two fp32
+ *          roundings each, as first_occupied);  x_mean = (float)((double)x0 + ((double)sum_ix / n + 0.5) * (double)cell), one operation
+ *          at a time, y_mean likewise;  h_max;  fill = (float)((double)n / ((double)(ix_max - ix_min + 1) * (double)(iy_max - iy_min + 1)))
+ *   rows at or beyond counts[b] are all zero in both tables
+ *   labels int32 [B][GY][GX] = -1 where the cell is not occupied, the rank k where its component is kept and k < cap, -2 otherwise
+ *   counts, total int32 [B]
+ * Everything is a function of the component as a set: two calls give identical bytes.
+ * workspace: ocv_obstacles_workspace_bytes(B, GX, GY) = 64 bytes per cell + 4 per OCV_OBSTACLES_CHUNK cells of an image (0 for sizes the
+ * entry point refuses), 8-byte aligned; every byte of it is written by every call.  Its layout, n = B * GX * GY:  int64 [n] each of
+ * points, obstacle_points, sum_ix, sum_iy;  int32 [n] each of n, GX - 1 - ix_min, ix_max, GY - 1 - iy_min, iy_max;  uint32 [n] the key of
+ * h_max -- these records live AT THE ROOT's cell and are zero elsewhere --;  int32 [n] parent (after the call: the root's iy * GX + ix
+ * of every occupied cell, -1 elsewhere);  int32 [n] rank;  int32 [B][chunks] kept roots per chunk.
+ * At most seven launches on the stream (csrc/obstacles.hip): the zero fill of the records; union-find by smaller index in LDS per tile of
+ * OCV_OBSTACLES_TILE x OCV_OBSTACLES_TILE cells; the pairs across tile edges in memory (find, atomic min on the larger root, again while
+ * another caller was faster; skipped for a one-tile grid); the flattening with the statistics, merged on chip per 256 cells (equal-root
+ * runs of a wave by ocv_ground_grid_fwd's segmented reduction, then an LDS table keyed by root) into one set of global atomics per
+ * distinct root; the kept roots per chunk; ranks, rows, tail and counts; with `labels` the relabel pass.  A parent index only ever
+ * decreases, so every loop of the union-find ends by construction (csrc/union_find.hpp).  INTEGER atomics only.  No allocation, no
+ * synchronisation, nothing read on the host (capturable).  Images are independent: a batch can be filled by one call per image with
+ * offset pointers.
+ * -1 with a message before any launch on: a null state / workspace, all outputs null, link outside 1..3, min_cells < 1,
+ * min_obstacle_points < 0, cap < 1, non-positive sizes, B * GX * GY or B * cap * 8 at or above 2^31, GX or GY above 2^24, cell <= 0 or
+ * infinite, an infinite origin (or a NaN in any of these), the workspace not 8-byte aligned, another pointer but state not 4-byte aligned,
+ * a workspace that is too small.
+ * ocv_obstacles_set_dispatch(on_chip_merge): 1 (default) as above, 0 sends every cell's statistics straight to memory -- the same bytes,
+ * kept for the A/B of tools/measure_obstacles.py; -1 for another value. */
+#define OCV_OBSTACLES_TILE 32
+#define OCV_OBSTACLES_CHUNK 1024
+size_t ocv_obstacles_workspace_bytes(int B, int GX, int GY);
+int ocv_obstacles_set_dispatch(int on_chip_merge);
+int ocv_obstacles_fwd(const uint8_t* state, const int* count, const int* obstacle, const float* h_max, int B, int GX, int GY, float x0,
+                      float y0, float cell, int link, int min_cells, int min_obstacle_points, int cap, int* cells, float* metres,
+                      int* labels, int* counts, int* total, void* workspace, size_t workspace_bytes, ocv_stream_t stream);
 /* Ground plane of the final map, STATEMENT E (no counterpart in the reference; the statement the tests compare against is
  * tests/ground_plane_ref.py: fp32 torch on the CPU with one eager op per rounding, the solve in float64 one operation at a time.  The
  * counts, the moments and the stats match it EXACTLY; the pose within one fp32 step, equal bits expected).  It estimates, per image, the

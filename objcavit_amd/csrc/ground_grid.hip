@@ -26,8 +26,10 @@
 // The keep rule is the point cloud's (keep_pixel.hpp).  Every per-point operation is fp32 and rounded on its own (__fmul_rn & co., and
 // gg_mul of rounded_mul.hpp where a product feeds a sum: the library is built with contraction on); `/` is the IEEE division.
 #include "common.hpp"
+#include "float_key.hpp"
 #include "keep_pixel.hpp"
 #include "rounded_mul.hpp"
+#include "seg_reduce.hpp"
 #include "../../include/objcavit_hip.h"
 
 #include <math.h>
@@ -66,13 +68,6 @@ struct FinalArgs {
   long n;                                                // B * cells
   float y0, cell;
 };
-
-// order-preserving image of a float in the unsigned integers (a < b  <=>  key(a) < key(b), -0 below +0)
-__device__ __forceinline__ unsigned gg_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float gg_unkey(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
 
 __device__ __forceinline__ int gg_state(int count, int obstacle, int min_points, int min_obstacle) {
   return count < min_points ? 0 : (obstacle >= min_obstacle ? 2 : 1);
@@ -134,21 +129,17 @@ __global__ __launch_bounds__(GG_THREADS) void grid_accumulate_kernel(GridArgs p)
     }
     if (__ballot(cell >= 0) == 0ull) continue;           // (wave-uniform)
     // 1. runs of consecutive lanes with the same cell: the run's first lane ends up with the run's join
-    const int before = __shfl_up(cell, 1, OCV_WAVE);
-    const bool head = lane == 0 || before != cell;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long above = lane == OCV_WAVE - 1 ? 0ull : heads >> (lane + 1);      // bit j: lane + 1 + j starts a run
-#pragma unroll
-    for (int o = 1; o < OCV_WAVE; o <<= 1) {
+    const SegRuns runs = seg_runs(cell, lane);             // (seg_reduce.hpp, shared with csrc/obstacles.hip)
+    seg_reduce(runs, lane, [&](int o, bool take) {
       const int packed_o = __shfl_down(packed, o, OCV_WAVE), sum_o = __shfl_down(sum, o, OCV_WAVE);
       const unsigned nmin_o = __shfl_down(nmin, o, OCV_WAVE), mx_o = __shfl_down(mx, o, OCV_WAVE);
-      if (lane + o < OCV_WAVE && (above & ((1ull << o) - 1ull)) == 0ull) {                   // lane + o is of this lane's run
+      if (take) {                                          // lane + o is of this lane's run
         packed += packed_o; sum += sum_o;
         nmin = max(nmin, nmin_o); mx = max(mx, mx_o);
       }
-    }
+    });
     // 2. the leaders insert
-    if (head && cell >= 0) {
+    if (runs.head && cell >= 0) {
       unsigned slot = ((unsigned)cell * 2654435761u) >> (32 - GG_LOG_SLOTS);
       bool placed = false;
       for (int probe = 0; probe < GG_PROBES && !placed; ++probe) {

@@ -1,6 +1,7 @@
 """hip_ops readouts: what is read out of the predict path's final map (``frames.depth_finalize``) behind it -- per-box statistics
 (csrc/object_depth.hip), the point cloud (csrc/point_cloud.hip), the surface normals (csrc/surface_normals.hip), the bird's-eye occupancy
-grid (csrc/ground_grid.hip), the ground plane that poses it (csrc/ground_plane.hip) and, against ground truth, the depth error per box
+grid (csrc/ground_grid.hip), the obstacles its occupied cells form (csrc/obstacles.hip), the ground plane that poses it
+(csrc/ground_plane.hip) and, against ground truth, the depth error per box
 and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, launches on the current stream, ``out=`` writes straight into buffers the caller owns.  The checks the wrappers
 share are the four helpers in front of them."""
@@ -353,6 +354,82 @@ def ground_grid(depth: torch.Tensor, K: torch.Tensor, pose: torch.Tensor, grid: 
     return res
 
 
+OBSTACLES_WANT = ("cells", "metres", "counts", "total", "labels")
+OBSTACLES_TILE = 32               # include/objcavit_hip.h: OCV_OBSTACLES_TILE, the union-find runs in LDS per tile of 32 x 32 cells
+OBSTACLES_MAX_LINK = 3            # Statement O: link in 1..3
+OBSTACLES_COLUMNS = 8             # columns of a row of "cells" / "metres"
+
+
+def obstacles(state: torch.Tensor, spec: Tuple[float, float, float, int, int], count: Optional[torch.Tensor] = None,
+              obstacle: Optional[torch.Tensor] = None, h_max: Optional[torch.Tensor] = None, link: int = 1, min_cells: int = 1,
+              min_obstacle_points: int = 0, capacity: int = 64, want: Tuple[str, ...] = OBSTACLES_WANT, out: Optional[dict] = None,
+              workspace: Optional[torch.Tensor] = None, image_index: int = 0) -> dict:
+    """The occupied cells of a ground grid grouped into obstacles (Statement O of include/objcavit_hip.h): ``state`` uint8 [B, GY, GX]
+    and, where given, ``count`` / ``obstacle`` int32 and ``h_max`` fp32 of that shape -- ``ground_grid``'s outputs, on the device --,
+    ``spec`` = the grid's (x0, y0, cell, GX, GY).  Occupied cells (state 2) within ``link`` (1..3) cells of each other along both axes
+    belong to one component; a component of at least ``min_cells`` cells and ``min_obstacle_points`` obstacle points is kept, and the
+    kept ones are ranked by their smallest iy * GX + ix: nearest first, ties left to right.  -> {"cells": int32 [B, capacity, 8] = ix_min,
+    ix_max, iy_min, iy_max, n, points, obstacle_points, root; "metres": fp32 [B, capacity, 8] = x_min, x_max, y_min, y_max, x_mean, y_mean,
+    h_max, fill; "counts", "total": int32 [B], total = the number kept, counts = min(total, capacity); "labels": int32 [B, GY, GX] = -1
+    where the cell is not occupied, its component's rank where that is kept and below ``capacity``, -2 otherwise}, those that ``want``
+    names; rows at or beyond counts[b] are all zero; every element is written.  ``out``: {name: tensor} of caller-owned buffers [N, ...]
+    with N >= image_index + B; the B images are written at ``image_index`` and the dict returned holds the whole buffers.
+    ``workspace``: a uint8 device tensor of at least ``ocv_obstacles_workspace_bytes`` (default: the stream's workspace store).  At most
+    seven launches (ocv_obstacles_fwd) on the current stream, integer atomics only (two calls give the same bytes), nothing read on the
+    host: capturable with ``out`` and a warmed-up workspace."""
+    lib = _lib.load()
+    _req(state, "state", torch.uint8)
+    if state.dim() != 3:
+        raise ValueError(f"obstacles: expected state uint8 [B, GY, GX], got {tuple(state.shape)}")
+    B, GY, GX = (int(v) for v in state.shape)
+    if len(tuple(spec)) != 5:
+        raise ValueError(f"obstacles: spec must be the grid's (x0, y0, cell, GX, GY), got {spec}")
+    x0, y0, cell = (C.c_float(float(v)).value for v in tuple(spec)[:3])
+    if (int(spec[3]), int(spec[4])) != (GX, GY) or GX < 1 or GY < 1 or B < 1:
+        raise ValueError(f"obstacles: state {tuple(state.shape)} is not [B >= 1, GY, GX] of the grid {tuple(spec)}")
+    if not (0.0 < cell < float("inf")) or not abs(x0) < float("inf") or not abs(y0) < float("inf"):
+        raise ValueError(f"obstacles: cell must be > 0 and finite and the origin finite, got {tuple(spec)[:3]}")
+    for name, t, dtype in (("count", count, torch.int32), ("obstacle", obstacle, torch.int32), ("h_max", h_max, torch.float32)):
+        if t is not None:
+            _req(t, name, dtype)
+            if t.shape != state.shape:
+                raise ValueError(f"obstacles: {name} must have state's shape")
+    for name, v, lo in (("link", link, 1), ("min_cells", min_cells, 1), ("min_obstacle_points", min_obstacle_points, 0), ("capacity", capacity, 1)):
+        if isinstance(v, bool) or int(v) != v or int(v) < lo:
+            raise ValueError(f"obstacles: {name} must be an integer >= {lo}, got {v}")
+    if int(link) > OBSTACLES_MAX_LINK:
+        raise ValueError(f"obstacles: link must be in 1..{OBSTACLES_MAX_LINK}, got {link}")
+    cap = int(capacity)
+    if B * cap * OBSTACLES_COLUMNS >= 1 << 31:
+        raise ValueError(f"obstacles: {B} x {cap} rows are too many (B * capacity * 8 below 2^31)")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(OBSTACLES_WANT):
+        raise ValueError(f"obstacles: want must name some of {OBSTACLES_WANT} (got {want})")
+    shapes = {"cells": ((cap, OBSTACLES_COLUMNS), torch.int32), "metres": ((cap, OBSTACLES_COLUMNS), torch.float32),
+              "counts": ((), torch.int32), "total": ((), torch.int32), "labels": ((GY, GX), torch.int32)}
+    res, at = _image_buffers(out, want, shapes, B, image_index, state.device, "obstacles")
+    need = int(lib.ocv_obstacles_workspace_bytes(B, GX, GY))
+    if need == 0:
+        raise ValueError(f"obstacles: a grid of {B} x {GY} x {GX} cells is too large (B * GX * GY below 2^31, GX and GY at most 2^24)")
+    if workspace is None:
+        from ._core import workspace as _workspace
+        workspace = _workspace(need, state.device, "obstacles")
+    else:
+        _req(workspace, "workspace", torch.uint8)
+    with timed("obstacles"):
+        check(lib.ocv_obstacles_fwd(state.data_ptr(), _ptr(count), _ptr(obstacle), _ptr(h_max), B, GX, GY, x0, y0, cell, int(link),
+                                    int(min_cells), int(min_obstacle_points), cap, at.get("cells"), at.get("metres"), at.get("labels"),
+                                    at.get("counts"), at.get("total"), workspace.data_ptr(), int(workspace.numel()), _stream()),
+              "ocv_obstacles_fwd")
+    return res
+
+
+def obstacles_set_dispatch(on_chip_merge: bool = True) -> None:
+    """The statistics pass of ``obstacles`` with (default) or without its on-chip merge: the same bytes either way; the A/B of
+    tools/measure_obstacles.py."""
+    check(_lib.load().ocv_obstacles_set_dispatch(1 if on_chip_merge else 0), "ocv_obstacles_set_dispatch")
+
+
 GROUND_PLANE_WANT = ("pose", "stats", "count", "moments")
 GROUND_PLANE_TILE = 1024              # include/objcavit_hip.h: OCV_GROUND_PLANE_TILE, candidates of the strided grid per workgroup
 GROUND_PLANE_MAX_HYPOTHESES = 1024    # OCV_GROUND_PLANE_MAX_HYPOTHESES
@@ -453,4 +530,5 @@ def ground_plane_workspace_views(workspace: torch.Tensor, B: int, T: int) -> dic
 __all__ = ["ground_plane", "ground_plane_workspace_views", "GROUND_PLANE_BATCH", "GROUND_PLANE_WANT", "GROUND_PLANE_TILE", "GROUND_PLANE_MAX_HYPOTHESES", "GROUND_PLANE_MAX_CANDIDATES",
            "GROUND_PLANE_MOMENTS", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics", "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
            "unproject_grid", "UNPROJECT_TILE", "depth_normals", "normals_gather", "NORMALS_WANT", "NORMALS_MAX_RADIUS",
-           "ground_grid", "GROUND_GRID_WANT", "GROUND_GRID_TILE", "GROUND_GRID_MAX_HEIGHT"]
+           "ground_grid", "GROUND_GRID_WANT", "GROUND_GRID_TILE", "GROUND_GRID_MAX_HEIGHT", "obstacles", "obstacles_set_dispatch", "OBSTACLES_WANT",
+           "OBSTACLES_TILE", "OBSTACLES_MAX_LINK", "OBSTACLES_COLUMNS"]

@@ -28,6 +28,7 @@ from .pixel_formats import PixelFormat, PlanarFrames
 from .point_cloud import PointCloud
 from .surface_normals import DEFAULT_EDGE_RATIO, DEFAULT_RADIUS, SurfaceNormals
 from .ground_grid import DEFAULTS as _GROUND_DEFAULTS, GroundGrid, grid_of as _grid_of, ground_pose as _ground_pose
+from .obstacles import DEFAULTS as _OBSTACLE_DEFAULTS, GRID_INPUTS as _OBSTACLE_INPUTS, Obstacles
 from .ground_plane import DEFAULTS as _PLANE_DEFAULTS, GroundPlane, cos_of_tilt as _cos_of_tilt, plane_triples as _plane_triples
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
@@ -250,6 +251,31 @@ def _ground_options(ground_grid, min_depth: float, max_depth: float, plane: bool
     return {**out, **_pixel_filter("ground_grid", opts, min_depth, max_depth)}
 
 
+_OBSTACLE_KEYS = ("link", "min_cells", "min_obstacle_points", "capacity", "labels")
+
+
+def _obstacle_options(obstacles, ground: bool) -> Optional[dict]:
+    """The ``obstacles`` keyword of both predictors: None (no list) or a dict with some of ``_OBSTACLE_KEYS``.  Defaults: 8-connectivity
+    (link 1), obstacles of at least two cells, no threshold on their obstacle points, 64 rows per image, no label map.  It reads the grid
+    of the same step (``ground``: whether the ``ground_grid`` keyword is given; without it the keyword is refused)."""
+    if obstacles is None:
+        return None
+    opts = _options("obstacles", obstacles, _OBSTACLE_KEYS)
+    if not ground:
+        raise ValueError("obstacles: the list is made from the grid of the same step -- it needs the ground_grid= keyword beside it "
+                         "(ground_grid={} takes the defaults)")
+    out = {}
+    for name, lo in (("link", 1), ("min_cells", 1), ("min_obstacle_points", 0), ("capacity", 1)):
+        v = opts.get(name, _OBSTACLE_DEFAULTS[name])
+        if isinstance(v, bool) or int(v) != v or int(v) < lo:
+            raise ValueError(f"obstacles: {name} must be an integer >= {lo}, got {v}")
+        out[name] = int(v)
+    if out["link"] > hip_ops.OBSTACLES_MAX_LINK:
+        raise ValueError(f"obstacles: link must be in 1..{hip_ops.OBSTACLES_MAX_LINK}, got {out['link']}")
+    out["labels"] = bool(opts.get("labels", _OBSTACLE_DEFAULTS["labels"]))
+    return out
+
+
 def _cloud_want(cloud: Optional[dict]) -> Tuple[str, ...]:
     """The maps a point cloud's (or a ground grid's) filters read beyond "depth": they are made for it (and ``bin_stats`` turned on)
     even when ``want`` leaves them out."""
@@ -382,14 +408,30 @@ def _run_ground(ends, step, made) -> GroundGrid:
             ent[key] = o["pose"].expand(B, 12).contiguous().to(dev)
         pose = ent[key]
     dtypes = {"count": torch.int32, "obstacle": torch.int32, "state": torch.uint8}
+    # the obstacle list reads state, count, obstacle and h_max: they are made for it even when the grid's ``want`` leaves them out (and
+    # are then not handed out) -- the ``_cloud_want`` rule
+    extra = _OBSTACLE_INPUTS if ends.obstacles is not None else ()
+    make = tuple(n for n in hip_ops.GROUND_GRID_WANT if n in o["want"] or n in extra)
     bufs = {n: torch.empty((B, GX) if n == "first_occupied" else (B, GY, GX), dtype=dtypes.get(n, torch.float32), device=dev)
-            for n in o["want"]}
+            for n in make}
     for _, s, _, _, K, conf, std in _per_frame(ends, step, dev, *_filter_maps(maps, o)):
         hip_ops.ground_grid(depth[s], K, pose[s], o["grid"], band=o["band"], obstacle_height=o["obstacle_height"],
                             min_points=o["min_points"], min_obstacle_points=o["min_obstacle_points"], stride=o["stride"], near=o["near"],
                             far=o["far"], confidence=conf, min_confidence=o["min_confidence"], depth_std=std, max_std=o["max_std"],
-                            want=o["want"], out=bufs, image_index=s.start)
-    return GroundGrid(*(bufs.get(n) for n in hip_ops.GROUND_GRID_WANT), x0=x0, y0=y0, cell=cell)
+                            want=make, out=bufs, image_index=s.start)
+    made["ground_buffers"] = bufs
+    return GroundGrid(*(bufs.get(n) if n in o["want"] else None for n in hip_ops.GROUND_GRID_WANT), x0=x0, y0=y0, cell=cell)
+
+
+def _run_obstacles(ends, step, made) -> Obstacles:
+    """The obstacle list of a step's grid (Statement O, objcavit_amd/obstacles.py): one call (at most seven launches) for the batch, on
+    the grid's own buffers behind its launches on the same stream -- the grid's cells are per image whatever the frames' sizes."""
+    o, g = ends.obstacles, made["ground_buffers"]
+    x0, y0, cell, GX, GY = ends.ground["grid"]
+    want = tuple(n for n in hip_ops.OBSTACLES_WANT if n != "labels" or o["labels"])
+    res = hip_ops.obstacles(g["state"], (x0, y0, cell, GX, GY), count=g["count"], obstacle=g["obstacle"], h_max=g["h_max"], link=o["link"],
+                            min_cells=o["min_cells"], min_obstacle_points=o["min_obstacle_points"], capacity=o["capacity"], want=want)
+    return Obstacles(*(res.get(n) for n in hip_ops.OBSTACLES_WANT), x0=x0, y0=y0, cell=cell)
 
 
 # One entry per output behind the final map, IN THE ORDER OF THEIR LAUNCHES.  keyword: the predictors' keyword; attr: the attribute of the
@@ -414,23 +456,31 @@ READOUTS = (
     _Readout("ground_grid", "ground", "ground", lambda kw, lo, hi: _ground_options(kw["ground_grid"], lo, hi, kw["ground_plane"] is not None),
              lambda o: ("depth",) + _cloud_want(o), ("K",), _run_ground, slice(None)),
 )
-for _r in READOUTS:
+# The readouts of a READOUT: they read no final map but the buffers of an entry above, of the same step on the same stream, and run
+# behind all of READOUTS in this order.  ``obstacles`` reads the grid's and is refused without the ``ground_grid`` keyword.
+DERIVED_READOUTS = (
+    _Readout("obstacles", "obstacles", "obstacles", lambda kw, lo, hi: _obstacle_options(kw["obstacles"], kw["ground_grid"] is not None),
+             lambda o: (), ("K",), _run_obstacles, slice(5)),
+)
+ALL_READOUTS = READOUTS + DERIVED_READOUTS
+for _r in ALL_READOUTS:
     setattr(PredictResult, _r.attr, None)          # an ATTRIBUTE, not a field: ``PredictResult``'s fields are what they were
 
 
 class _ObjectsResult(PredictResult):
     """A ``PredictResult`` -- same fields, same tuple -- whose attributes named in ``READOUTS`` (``objects`` / ``points`` /
-    ``object_metrics`` / ``normals`` / ``plane`` / ``ground``) hold the step's ``ObjectDepths`` / ``PointCloud`` / ``ObjectMetrics`` /
-    ``SurfaceNormals`` / ``GroundPlane`` / ``GroundGrid``; each is a keyword of its own and survives ``_replace``."""
+    ``object_metrics`` / ``normals`` / ``plane`` / ``ground``) or in ``DERIVED_READOUTS`` (``obstacles``) hold the step's ``ObjectDepths`` /
+    ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals`` / ``GroundPlane`` / ``GroundGrid`` / ``Obstacles``; each is a keyword of its own
+    and survives ``_replace``."""
 
     def __new__(cls, *fields, **kw):
-        made = {r.attr: kw.pop(r.attr, None) for r in READOUTS}
+        made = {r.attr: kw.pop(r.attr, None) for r in ALL_READOUTS}
         self = super().__new__(cls, *fields, **kw)
         self.__dict__.update(made)
         return self
 
     def _replace(self, **kw):
-        return _ObjectsResult(*PredictResult(*self)._replace(**kw), **{r.attr: getattr(self, r.attr) for r in READOUTS})
+        return _ObjectsResult(*PredictResult(*self)._replace(**kw), **{r.attr: getattr(self, r.attr) for r in ALL_READOUTS})
 
 
 class _Step(namedtuple("_Step", ["depth_gt", "boxes", "K", "frames", "pose", "size"])):
@@ -550,7 +600,7 @@ class _Ends:
 
     def __init__(self, args, *, flip_tta: bool = True, loss: bool = False, colormap=None, vmin=None, vmax=None, u16_scale=None, crop=None,
                  resize=None, pixel_format=None, lens=None, **readouts):
-        """The predictors' keywords, by keyword; ``readouts``: those named in ``READOUTS``."""
+        """The predictors' keywords, by keyword; ``readouts``: those named in ``ALL_READOUTS``."""
         self.args, self.flip_tta, self.loss, self.crop = args, flip_tta, loss, crop
         self.fmt = None if pixel_format is None else PixelFormat.of(pixel_format)      # None: rgb24 through the rgb24 calls
         self.resize = _model_size(resize)
@@ -561,13 +611,13 @@ class _Ends:
         self.lens = lens
         self._rect = (None, None)                    # (the frame list last ingested through the lens with ``resize``, its RGB24 copies)
         self.min_depth, self.max_depth = _depth_range(args)
-        given = {r.keyword: readouts.pop(r.keyword, None) for r in READOUTS}
+        given = {r.keyword: readouts.pop(r.keyword, None) for r in ALL_READOUTS}
         if readouts:
             raise TypeError(f"_Ends: unknown keyword(s) {sorted(readouts)}")
-        for r in READOUTS:                           # .errors, .readout, .cloud, .normals, .plane, .ground: the parsed keyword or None
+        for r in ALL_READOUTS:                       # .errors, .readout, .cloud, .normals, .plane, .ground, .obstacles: the parsed keyword or None
             setattr(self, r.options, r.parse(given, self.min_depth, self.max_depth))
         self.cloud_normals = _cloud_normals(given["point_cloud"])          # a normal per point of the cloud
-        self.readouts = tuple((r, r.maps(getattr(self, r.options))) for r in READOUTS if getattr(self, r.options) is not None)
+        self.readouts = tuple((r, r.maps(getattr(self, r.options))) for r in ALL_READOUTS if getattr(self, r.options) is not None)
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -775,7 +825,7 @@ class _Ends:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
         the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  Behind them
         every readout of ``READOUTS`` whose keyword is set and whose ``needs`` the step has, in that order: the per-object error right
-        behind the metric launch, the object readout, the point cloud, the normals, the ground plane, the occupancy grid.  The maps they
+        behind the metric launch, the object readout, the point cloud, the normals, the ground plane, the occupancy grid, then ``DERIVED_READOUTS``: the obstacle list of that grid.  The maps they
         read are made even when ``want`` leaves them out (and are then not handed out)."""
         asked = want
         live = [r for r, _ in self.readouts if None not in [getattr(step, n) for n in r.needs]]
@@ -911,6 +961,13 @@ class Predictor:
     the normals and in front of the grid, and the result's ``plane`` ATTRIBUTE holds the ``GroundPlane`` (pose [B, 12], stats [B, 4]; None
     otherwise); where no plane is found the pose is the prior's.  ``ground_grid=dict(pose="plane")`` makes the grid of the same step read
     that pose on the device (refused at construction without ``ground_plane=``); ``camera_pose=`` of a call still wins.  Pass it by keyword.
+    ``obstacles``: None, or a dict with some of ``link`` (1: 8-connectivity; 2 or 3 bridge one- or two-cell holes), ``min_cells`` (2),
+    ``min_obstacle_points`` (0), ``capacity`` (64 rows per image), ``labels`` (False: the per-cell label map) -- the occupied cells of the
+    step's grid grouped into obstacles, nearest first (objcavit_amd/obstacles.py, Statement O).  Refused at construction without
+    ``ground_grid=``.  With it, at most seven more launches behind the grid's read its buffers on the device, and the result's
+    ``obstacles`` ATTRIBUTE holds the ``Obstacles`` (cells, metres [B, capacity, 8], counts, total [B], labels or None; None otherwise).
+    The grid's ``state``, ``count``, ``obstacle`` and ``h_max`` are made for it even when the grid's ``want`` leaves them out;
+    ``result.ground`` still hands out only what was asked for.  Pass it by keyword.
     ``object_metrics``: None, or a dict with some of ``shrink`` / ``regions`` -- the depth error per box and over objects against
     background (objcavit_amd/object_metrics.py).  With it, a call that has both ``depth_gt`` and ``boxes=`` (in pixels of the ground
     truth's grid) issues one more call right behind the metric launch, on the tensors that launch reads, and the result's
@@ -919,14 +976,15 @@ class Predictor:
 
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
-                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None, pixel_format=None,
+                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None,
+                 obstacles: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
                           resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
                           object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid,
-                          ground_plane=ground_plane)
+                          ground_plane=ground_plane, obstacles=obstacles)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -964,6 +1022,7 @@ class PipelinedPredictor(_SlotPipeline):
     stream behind the cloud, no host read.  ``ground_grid`` / ``submit(..., camera_pose=)``: as ``Predictor``'s, on the slot's stream behind
     the normals; the pose is uploaded in ``submit`` and held like the frames.  ``ground_plane``: as ``Predictor``'s, on the slot's stream
     between the normals and the grid, no host read; with ``ground_grid=dict(pose="plane")`` the grid reads the step's own estimate.
+    ``obstacles``: as ``Predictor``'s, on the slot's stream behind the grid, no host read; its tensors are recorded like the grid's.
     ``object_metrics``: as ``Predictor``'s, on the slot's stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
     graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
@@ -983,7 +1042,8 @@ class PipelinedPredictor(_SlotPipeline):
     def __init__(self, model, args, example_frames: Frames, slots: int = 4, object_capacity: Optional[int] = None,
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
-                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None, pixel_format=None,
+                 ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None,
+                 obstacles: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
@@ -992,7 +1052,7 @@ class PipelinedPredictor(_SlotPipeline):
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
                           resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
                           object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid,
-                          ground_plane=ground_plane)
+                          ground_plane=ground_plane, obstacles=obstacles)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.plane) or _cloud_want(self.ends.ground):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
