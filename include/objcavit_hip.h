@@ -46,7 +46,8 @@ typedef void* ocv_stream_t;
  * ocv_depth_normals_fwd / ocv_normals_gather_fwd (surface normals of the final map, Statement N),
  * ocv_ground_grid_workspace_bytes / ocv_ground_grid_fwd (bird's-eye occupancy grid of the final map, Statement G),
  * ocv_ground_plane_workspace_bytes / ocv_ground_plane_fwd (ground plane of the final map, Statement E),
- * ocv_obstacles_workspace_bytes / ocv_obstacles_set_dispatch / ocv_obstacles_fwd (obstacle list of the ground grid, Statement O);
+ * ocv_obstacles_workspace_bytes / ocv_obstacles_set_dispatch / ocv_obstacles_fwd (obstacle list of the ground grid, Statement O),
+ * ocv_ground_fuse_fwd (ground memory: the grid fused over time, Statement F);
  * 4: round 5 REMOVED the opt-in entry points that lost their A/Bs (ocv_tap_interp_skip_fwd, the squeeze-excite tail
  * family ocv_*_se_fwd / ocv_se_fold_gate_weights_fwd / ocv_se_tail_supported, ocv_conv3x3_winograd_split_fwd F(2x2)) and added the range
  * guard (ocv_range_flag_set, ocv_range_flag_take_fwd, ocv_attention_set_fp32_range), bin head route 4, ocv_mha_few_keys_h2_set_dispatch;
@@ -1000,6 +1001,49 @@ int ocv_obstacles_set_dispatch(int on_chip_merge);
 int ocv_obstacles_fwd(const uint8_t* state, const int* count, const int* obstacle, const float* h_max, int B, int GX, int GY, float x0,
                       float y0, float cell, int link, int min_cells, int min_obstacle_points, int cap, int* cells, float* metres,
                       int* labels, int* counts, int* total, void* workspace, size_t workspace_bytes, ocv_stream_t stream);
+/* Ground memory, the occupancy grid fused over time, STATEMENT F (no counterpart in the reference; the statement the tests compare against
+ * is tests/ground_memory_ref.py, numpy fp32 on the CPU with one operation per rounding: the kernel matches it EXACTLY, not within a
+ * tolerance).  Per-cell evidence, carried from step to step through the vehicle's motion and updated by each step's grid.
+ * INPUTS, per image b of B independent camera streams:  state uint8 [B][GY][GX], this step's grid state (0 unknown, 1 free, 2 occupied);
+ * nullable h_max fp32 [B][GY][GX], this step's grid h_max;  nullable prev_evidence int16 [B][GY][GX], the evidence the previous step
+ * wrote (null = all zero: the first step);  nullable prev_h fp32 [B][GY][GX], the previous step's fused h_max;  motion fp32 [B][4] =
+ * (c, s, tx, ty) in DEVICE memory, 16-byte aligned: a point at p in the current ground frame was at
+ * (c * p.x - s * p.y + tx,  s * p.x + c * p.y + ty) in the previous step's ground frame -- an image with any non-finite motion value
+ * FORGETS: it carries nothing (that is how a stream is reset);  the grid's x0, y0, cell, GX, GY with Statement G's limits;  integers
+ * free >= 0, occupied >= 0, decay >= 0, limit >= 1, free_at >= 1, occupied_at >= 1, each at most 16383.
+ * PER OUTPUT CELL (iy, ix).  Every fp32 operation is rounded on its own (a product that feeds a sum too), `/` the IEEE division, sums
+ * left to right:
+ *   xc = x0 + (float(ix) + 0.5f) * cell          yc = y0 + (float(iy) + 0.5f) * cell
+ *   px = (c * xc - s * yc) + tx                  py = (s * xc + c * yc) + ty
+ *   fxi = floorf((px - x0) / cell)               fyi = floorf((py - y0) / cell)
+ *   inside  = the image does not forget and 0 <= fxi < GX and 0 <= fyi < GY   (compared as floats: NaN fails)
+ *   carried = inside and prev_evidence given ? prev_evidence[b][int(fyi)][int(fxi)] : 0          (the nearest cell; int32 from here on)
+ *   m = |carried| - decay;   faded = m > 0 ? sign(carried) * m : 0
+ *   hit = state == 2 ? +occupied : state == 1 ? -free : 0
+ *   evidence = clamp(faded + hit, -limit, +limit)                                                 (stored as int16)
+ *   fused state = evidence >= occupied_at ? 2 : evidence <= -free_at ? 1 : 0
+ *   h = -inf;  if (h_max given and state == 2) h = h_max[b][iy][ix]
+ *              if (prev_h given and inside and carried > 0 and prev_h[b][int(fyi)][int(fxi)] > h) h = that value
+ *   fused h_max = (evidence > 0 and h > -inf) ? h : 0
+ * PER LATERAL COLUMN:  first_occupied fp32 [B][GX] = y0 + float(iy) * cell (two fp32 roundings, Statement G's rule) of the smallest iy
+ * whose FUSED state is 2, +inf when there is none.
+ * OUTPUTS, each nullable, at least one given, EVERY element of a given output written:  evidence int16 [B][GY][GX];  fused state uint8
+ * [B][GY][GX];  fused h_max fp32 [B][GY][GX];  first_occupied fp32 [B][GX].
+ * The warp is a gather and the column scan evaluates the statement a second time, so NO OUTPUT MAY OVERLAP AN INPUT: evidence / fused
+ * h_max over prev_evidence / prev_h (a ping-pong in place) is refused, and so is any other pair.
+ * ONE launch on the stream (csrc/ground_fuse.hip), no workspace, no atomics: 256-thread workgroups, one per (image, tile of
+ * OCV_GROUND_FUSE_TILE x OCV_GROUND_FUSE_TILE cells) -- square, so that the tile's footprint in the previous map stays compact under
+ * any rotation -- and, with first_occupied, one per (image, 8 columns) for the column scan.  Two calls give identical bytes.  No
+ * allocation, no synchronisation, nothing read on the host (capturable).  Images are independent: a batch can be filled by one call per
+ * image with offset pointers.
+ * -1 with a message before the launch on: a null state / motion, all outputs null, non-positive sizes, B * GX * GY at or above 2^31, GX
+ * or GY above 2^24, cell <= 0 or infinite, an infinite origin (or a NaN in any of these), an integer outside its range, motion not
+ * 16-byte aligned, an fp32 tensor not 4-byte aligned, an int16 tensor not 2-byte aligned, an output that overlaps an input. */
+#define OCV_GROUND_FUSE_TILE 16
+int ocv_ground_fuse_fwd(const uint8_t* state, const float* h_max, const int16_t* prev_evidence, const float* prev_h, const float* motion,
+                        int B, int GX, int GY, float x0, float y0, float cell, int free, int occupied, int decay, int limit, int free_at,
+                        int occupied_at, int16_t* evidence, uint8_t* fused_state, float* fused_h_max, float* first_occupied,
+                        ocv_stream_t stream);
 /* Ground plane of the final map, STATEMENT E (no counterpart in the reference; the statement the tests compare against is
  * tests/ground_plane_ref.py: fp32 torch on the CPU with one eager op per rounding, the solve in float64 one operation at a time.  The
  * counts, the moments and the stats match it EXACTLY; the pose within one fp32 step, equal bits expected).  It estimates, per image, the

@@ -163,6 +163,8 @@ PROTOTYPES = {
     "ocv_obstacles_set_dispatch": (C.c_int, [C.c_int]),
     "ocv_obstacles_fwd": (C.c_int, [_u8p, C.c_void_p, C.c_void_p, _f32p] + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_int] * 4 +
                           [C.c_void_p, _f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _stream]),
+    "ocv_ground_fuse_fwd": (C.c_int, [_u8p, _f32p, C.c_void_p, _f32p, _f32p] + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_int] * 6 +
+                            [C.c_void_p, _u8p, _f32p, _f32p, _stream]),
     "ocv_ground_plane_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
     "ocv_ground_plane_fwd": (C.c_int, [_f32p, _f32p, C.c_void_p, _f32p, _f32p, _f32p] + [C.c_int] * 6 + [C.c_float] * 10 + [C.c_int] +
                              [_f32p, C.c_void_p, C.c_void_p, C.c_size_t, _stream]),

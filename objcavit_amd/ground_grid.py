@@ -20,9 +20,11 @@ z forward) goes to the GROUND frame g = R P + t: g_0 lateral (right), g_1 forwar
 [R | t].  Everything per point is fp32 with every operation rounded on its own, everything per cell integer arithmetic (integer atomics
 on chip and in memory), so the grid is the same bits on every call and equal to the statement (Statement G of include/objcavit_hip.h,
 tests/ground_grid_ref.py), not merely close to it.  Cells between the camera and the first hit stay "unknown" unless they are seen: there
-is no ray casting, no fusion over time, and the pose is the caller's (an IMU's, a calibration's), not estimated from the map -- unless the
+is no ray casting, and the pose is the caller's (an IMU's, a calibration's), not estimated from the map -- unless the
 predictors' ``ground_plane=`` keyword estimates it in the same step and ``ground_grid=dict(pose="plane")`` reads it
-(objcavit_amd/ground_plane.py).
+(objcavit_amd/ground_plane.py).  A grid is ONE frame's answer and flickers as the depth map does; fusing it over time -- per-cell
+evidence carried from step to step through the vehicle's motion -- is ``objcavit_amd/ground_memory.py`` (the predictors'
+``ground_memory=`` keyword), which reads this grid's ``state`` and ``h_max``.
 """
 from __future__ import annotations
 

@@ -14,7 +14,7 @@ One module per kernel family (round 5; the single 2 100-line file of rounds 1 - 
     encoder  EfficientNet NHWC blocks (stem, 1x1, depthwise + squeeze-excite, fused expand + depthwise), validation metrics
     frames   predict path: uint8 / uint16 frame ingest (crop, antialiased resize, normalise, mirror), final depth map (fp32, 16-bit, colour-mapped)
     readouts behind the final map: per-box depth statistics, the map as compacted 3-D points, as surface normals and as a bird's-eye
-             occupancy grid, that grid's obstacles, the ground plane's pose, depth error per box / region
+             occupancy grid, that grid fused over time, its obstacles, the ground plane's pose, depth error per box / region
 Every name stays reachable as ``hip_ops.<name>`` (this file re-exports the modules' namespaces; state objects such as
 ``ROUTE_REPORT`` / ``_TLS`` are shared, not copied).
 """

@@ -1,6 +1,7 @@
 """hip_ops readouts: what is read out of the predict path's final map (``frames.depth_finalize``) behind it -- per-box statistics
 (csrc/object_depth.hip), the point cloud (csrc/point_cloud.hip), the surface normals (csrc/surface_normals.hip), the bird's-eye occupancy
-grid (csrc/ground_grid.hip), the obstacles its occupied cells form (csrc/obstacles.hip), the ground plane that poses it
+grid (csrc/ground_grid.hip), that grid fused over time (csrc/ground_fuse.hip), the obstacles its occupied cells form
+(csrc/obstacles.hip), the ground plane that poses it
 (csrc/ground_plane.hip) and, against ground truth, the depth error per box
 and per region (csrc/object_metrics.hip).  Same rules as every wrapper: operands are checked on the host, CPU tensors raise
 ``HipLibraryError``, launches on the current stream, ``out=`` writes straight into buffers the caller owns.  The checks the wrappers
@@ -430,6 +431,69 @@ def obstacles_set_dispatch(on_chip_merge: bool = True) -> None:
     check(_lib.load().ocv_obstacles_set_dispatch(1 if on_chip_merge else 0), "ocv_obstacles_set_dispatch")
 
 
+GROUND_FUSE_WANT = ("evidence", "state", "h_max", "first_occupied")
+GROUND_FUSE_TILE = 16             # include/objcavit_hip.h: OCV_GROUND_FUSE_TILE, a workgroup fuses a tile of 16 x 16 cells
+GROUND_FUSE_MAX = 16383           # Statement F: the largest value of each integer option (sums of two stay inside an int16's range)
+
+
+def ground_fuse(state: torch.Tensor, spec: Tuple[float, float, float, int, int], motion: torch.Tensor,
+                prev_evidence: Optional[torch.Tensor] = None, h_max: Optional[torch.Tensor] = None, prev_h: Optional[torch.Tensor] = None,
+                free: int = 2, occupied: int = 4, decay: int = 1, limit: int = 32, free_at: int = 4, occupied_at: int = 6,
+                want: Tuple[str, ...] = GROUND_FUSE_WANT, out: Optional[dict] = None, image_index: int = 0) -> dict:
+    """One step of the ground memory (Statement F of include/objcavit_hip.h): ``state`` uint8 [B, GY, GX] and, where given, ``h_max`` fp32
+    of that shape -- this step's ``ground_grid`` outputs, on the device --, ``spec`` = the grid's (x0, y0, cell, GX, GY), ``motion`` fp32
+    [B, 4] on the device = (cos, sin, tx, ty): a point at p in this step's ground frame was at R p + t in the previous step's
+    (``objcavit_amd.ground_memory.ego_motion``); ``prev_evidence`` int16 / ``prev_h`` fp32 [B, GY, GX]: the "evidence" / "h_max" the
+    previous step returned (None: nothing yet).  Every cell carries the evidence of the previous map's cell its centre was in (the nearest
+    one; none outside the grid, or when its image's motion is not finite: that image forgets), faded towards 0 by ``decay``, adds
+    +``occupied`` where this step's state is 2 and -``free`` where it is 1, and is clamped to +-``limit``.  -> {"evidence": int16
+    [B, GY, GX]; "state": uint8 [B, GY, GX], 2 where evidence >= ``occupied_at``, 1 where evidence <= -``free_at``, else 0; "h_max": fp32
+    [B, GY, GX], the larger of this step's h_max (where its state is 2) and the carried one (where the carried evidence is positive), 0
+    where the evidence is not positive; "first_occupied": fp32 [B, GX] of the fused state, as the grid's}, those that ``want`` names;
+    every element is written.  ``out``: {name: tensor} of caller-owned buffers [N, ...] with N >= image_index + B; the B images are
+    written at ``image_index`` and the dict returned holds the whole buffers.  No output may overlap an input (the warp is a gather: it
+    cannot run in place).  One launch (ocv_ground_fuse_fwd) on the current stream, no workspace, no atomics (two calls give the same
+    bytes), nothing read on the host: capturable with ``out``."""
+    lib = _lib.load()
+    _req(state, "state", torch.uint8)
+    if state.dim() != 3:
+        raise ValueError(f"ground_fuse: expected state uint8 [B, GY, GX], got {tuple(state.shape)}")
+    B, GY, GX = (int(v) for v in state.shape)
+    if len(tuple(spec)) != 5:
+        raise ValueError(f"ground_fuse: spec must be the grid's (x0, y0, cell, GX, GY), got {spec}")
+    x0, y0, cell = (C.c_float(float(v)).value for v in tuple(spec)[:3])
+    if (int(spec[3]), int(spec[4])) != (GX, GY) or GX < 1 or GY < 1 or B < 1:
+        raise ValueError(f"ground_fuse: state {tuple(state.shape)} is not [B >= 1, GY, GX] of the grid {tuple(spec)}")
+    if not (0.0 < cell < float("inf")) or not abs(x0) < float("inf") or not abs(y0) < float("inf"):
+        raise ValueError(f"ground_fuse: cell must be > 0 and finite and the origin finite, got {tuple(spec)[:3]}")
+    if B * GX * GY >= 1 << 31 or GX > 1 << 24 or GY > 1 << 24:
+        raise ValueError(f"ground_fuse: a grid of {B} x {GY} x {GX} cells is too large (B * GX * GY below 2^31, GX and GY at most 2^24)")
+    _req(motion, "motion")
+    if tuple(motion.shape) != (B, 4):
+        raise ValueError(f"ground_fuse: motion must be fp32 [{B}, 4] = cos, sin, tx, ty, got {tuple(motion.shape)}")
+    for name, t, dtype in (("prev_evidence", prev_evidence, torch.int16), ("h_max", h_max, torch.float32), ("prev_h", prev_h, torch.float32)):
+        if t is not None:
+            _req(t, name, dtype)
+            if t.shape != state.shape:
+                raise ValueError(f"ground_fuse: {name} must have state's shape")
+    for name, v, lo in (("free", free, 0), ("occupied", occupied, 0), ("decay", decay, 0), ("limit", limit, 1), ("free_at", free_at, 1),
+                        ("occupied_at", occupied_at, 1)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= GROUND_FUSE_MAX:
+            raise ValueError(f"ground_fuse: {name} must be an integer in {lo}..{GROUND_FUSE_MAX}, got {v}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(GROUND_FUSE_WANT):
+        raise ValueError(f"ground_fuse: want must name some of {GROUND_FUSE_WANT} (got {want})")
+    dtypes = {"evidence": torch.int16, "state": torch.uint8}
+    shapes = {n: ((GX,) if n == "first_occupied" else (GY, GX), dtypes.get(n, torch.float32)) for n in GROUND_FUSE_WANT}
+    res, at = _image_buffers(out, want, shapes, B, image_index, state.device, "ground_fuse")
+    with timed("ground_fuse"):
+        check(lib.ocv_ground_fuse_fwd(state.data_ptr(), _ptr(h_max), _ptr(prev_evidence), _ptr(prev_h), motion.data_ptr(), B, GX, GY, x0, y0,
+                                      cell, int(free), int(occupied), int(decay), int(limit), int(free_at), int(occupied_at),
+                                      at.get("evidence"), at.get("state"), at.get("h_max"), at.get("first_occupied"), _stream()),
+              "ocv_ground_fuse_fwd")
+    return res
+
+
 GROUND_PLANE_WANT = ("pose", "stats", "count", "moments")
 GROUND_PLANE_TILE = 1024              # include/objcavit_hip.h: OCV_GROUND_PLANE_TILE, candidates of the strided grid per workgroup
 GROUND_PLANE_MAX_HYPOTHESES = 1024    # OCV_GROUND_PLANE_MAX_HYPOTHESES
@@ -531,4 +595,4 @@ __all__ = ["ground_plane", "ground_plane_workspace_views", "GROUND_PLANE_BATCH",
            "GROUND_PLANE_MOMENTS", "object_depth", "OBJECT_DEPTH_COLUMNS", "object_metrics", "OBJECT_METRICS_COLUMNS", "OBJECT_METRICS_MAX_BOXES", "depth_unproject",
            "unproject_grid", "UNPROJECT_TILE", "depth_normals", "normals_gather", "NORMALS_WANT", "NORMALS_MAX_RADIUS",
            "ground_grid", "GROUND_GRID_WANT", "GROUND_GRID_TILE", "GROUND_GRID_MAX_HEIGHT", "obstacles", "obstacles_set_dispatch", "OBSTACLES_WANT",
-           "OBSTACLES_TILE", "OBSTACLES_MAX_LINK", "OBSTACLES_COLUMNS"]
+           "OBSTACLES_TILE", "OBSTACLES_MAX_LINK", "OBSTACLES_COLUMNS", "ground_fuse", "GROUND_FUSE_WANT", "GROUND_FUSE_TILE", "GROUND_FUSE_MAX"]

@@ -17,7 +17,8 @@ in cells and (outer edges) in metres, the centroid of its cells' centres, the hi
 Connected components by union-find with union by smaller index, in LDS per tile of 32 x 32 cells and across tile edges in memory; the
 statistics are integer atomics at the component's root, so the list is the same bits on every call and equal to the statement (Statement
 O of include/objcavit_hip.h, tests/obstacles_ref.py), not merely close to it.  No tracking over time and no classification: a list of
-extents per frame."""
+extents per frame -- or, through ``FusedGrid.as_grid()`` / ``ground_memory=dict(obstacles=True)``, of the grid fused over time
+(objcavit_amd/ground_memory.py), whose cells do not flicker with the depth map; the rows are still not associated from step to step."""
 from __future__ import annotations
 
 from collections import namedtuple

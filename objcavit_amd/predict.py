@@ -29,6 +29,8 @@ from .point_cloud import PointCloud
 from .surface_normals import DEFAULT_EDGE_RATIO, DEFAULT_RADIUS, SurfaceNormals
 from .ground_grid import DEFAULTS as _GROUND_DEFAULTS, GroundGrid, grid_of as _grid_of, ground_pose as _ground_pose
 from .obstacles import DEFAULTS as _OBSTACLE_DEFAULTS, GRID_INPUTS as _OBSTACLE_INPUTS, Obstacles
+from .ground_memory import (OPTIONS as _MEMORY_OPTIONS, FusedGrid, check_want as _memory_want, ego_motion as _ego_motion,
+                            options_of as _memory_integers)
 from .ground_plane import DEFAULTS as _PLANE_DEFAULTS, GroundPlane, cos_of_tilt as _cos_of_tilt, plane_triples as _plane_triples
 from .validation import _SlotPipeline, _call, _depth_range, _empty_records, _forward_pair, _joint, _records, _split
 
@@ -276,6 +278,25 @@ def _obstacle_options(obstacles, ground: bool) -> Optional[dict]:
     return out
 
 
+_MEMORY_KEYS = _MEMORY_OPTIONS + ("obstacles", "want")
+
+
+def _memory_options(ground_memory, ground: bool) -> Optional[dict]:
+    """The ``ground_memory`` keyword of both predictors: None (no memory) or a dict with some of ``_MEMORY_KEYS``.  Defaults: those of
+    ``objcavit_amd.ground_memory`` (free 2, occupied 4, decay 1, limit 32, free_at 4, occupied_at 6), every output, and the obstacle list
+    (where the ``obstacles`` keyword asks for one) made from the frame's grid as without the memory; ``obstacles=True`` makes it from the
+    FUSED map instead.  It reads the grid of the same step (``ground``: whether the ``ground_grid`` keyword is given; without it the
+    keyword is refused)."""
+    if ground_memory is None:
+        return None
+    opts = _options("ground_memory", ground_memory, _MEMORY_KEYS)
+    if not ground:
+        raise ValueError("ground_memory: the memory fuses the grid of every step -- it needs the ground_grid= keyword beside it "
+                         "(ground_grid={} takes the defaults)")
+    return {**_memory_integers(opts), "obstacles": bool(opts.get("obstacles", False)),
+            "want": _memory_want(opts.get("want", hip_ops.GROUND_FUSE_WANT))}
+
+
 def _cloud_want(cloud: Optional[dict]) -> Tuple[str, ...]:
     """The maps a point cloud's (or a ground grid's) filters read beyond "depth": they are made for it (and ``bin_stats`` turned on)
     even when ``want`` leaves them out."""
@@ -408,9 +429,9 @@ def _run_ground(ends, step, made) -> GroundGrid:
             ent[key] = o["pose"].expand(B, 12).contiguous().to(dev)
         pose = ent[key]
     dtypes = {"count": torch.int32, "obstacle": torch.int32, "state": torch.uint8}
-    # the obstacle list reads state, count, obstacle and h_max: they are made for it even when the grid's ``want`` leaves them out (and
-    # are then not handed out) -- the ``_cloud_want`` rule
-    extra = _OBSTACLE_INPUTS if ends.obstacles is not None else ()
+    # the obstacle list reads state, count, obstacle and h_max, the memory state and h_max: they are made for them even when the grid's
+    # ``want`` leaves them out (and are then not handed out) -- the ``_cloud_want`` rule
+    extra = (_OBSTACLE_INPUTS if ends.obstacles is not None else ()) + (("state", "h_max") if ends.memory is not None else ())
     make = tuple(n for n in hip_ops.GROUND_GRID_WANT if n in o["want"] or n in extra)
     bufs = {n: torch.empty((B, GX) if n == "first_occupied" else (B, GY, GX), dtype=dtypes.get(n, torch.float32), device=dev)
             for n in make}
@@ -423,10 +444,61 @@ def _run_ground(ends, step, made) -> GroundGrid:
     return GroundGrid(*(bufs.get(n) if n in o["want"] else None for n in hip_ops.GROUND_GRID_WANT), x0=x0, y0=y0, cell=cell)
 
 
+def _run_memory(ends, step, made) -> FusedGrid:
+    """The ground memory's step (Statement F, objcavit_amd/ground_memory.py): one launch for the batch behind the grid's, on the grid's
+    ``state`` and ``h_max``, the evidence and fused ``h_max`` of the PREVIOUS step (``ends._memory``) and the step's motion; the outputs
+    are fresh tensors, and the memory then holds this step's.  The previous step may have run on another stream (a pipeline's slots):
+    the current stream waits for the event that step recorded behind its launch, this step records its own, and the previous step's
+    tensors are recorded for the current stream.  Only this launch is ordered; everything in front of it overlaps as before.
+    A step that runs a SECOND time (``PipelinedPredictor.collect`` re-runs a step whose fp16 range guard tripped, after the steps
+    behind it have run) is fused again from the previous evidence and motion it had read the first time -- kept in ``step.memory`` --
+    and does not advance the memory: its own ``FusedGrid`` is the re-run's, but THE STEPS BEHIND IT HAVE FUSED ITS FIRST MAP."""
+    o, g, rec = ends.memory, made["ground_buffers"], step.memory
+    state = g["state"]
+    B, dev = int(state.shape[0]), state.device
+    x0, y0, cell, GX, GY = ends.ground["grid"]
+    again = "prev" in rec
+    if not again:
+        if rec["reset"]:
+            ends._memory = None
+        rec["prev"] = ends._memory                           # None, or (evidence, h_max, the event behind the launch that wrote them)
+    prev = rec["prev"]
+    motion = rec["motion"]
+    if motion is None:
+        ent = ends._on(dev, False)
+        key = ("ego_identity", B)
+        if key not in ent:
+            ent[key] = _ego_motion().expand(B, 4).contiguous().to(dev)
+        motion = ent[key]
+    cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+    if prev is not None and tuple(prev[0].shape) != tuple(state.shape):
+        raise ValueError(f"ground_memory: the batch changed from {int(prev[0].shape[0])} to {B} stream(s) (pass reset=True)")
+    if prev is not None and not again and prev[2] is not None and cur is not None:
+        cur.wait_event(prev[2])
+    make = tuple(n for n in hip_ops.GROUND_FUSE_WANT if n in o["want"] or n in ("evidence", "h_max") or (o["obstacles"] and n == "state"))
+    res = hip_ops.ground_fuse(state, (x0, y0, cell, GX, GY), motion, prev_evidence=None if prev is None else prev[0], h_max=g["h_max"],
+                              prev_h=None if prev is None else prev[1], want=make, **{n: o[n] for n in _MEMORY_OPTIONS})
+    if not again:
+        event = None
+        if cur is not None:
+            event = torch.cuda.Event()
+            event.record(cur)
+            for t in (prev or ())[:2]:
+                t.record_stream(cur)                         # made on the previous step's stream, read by this launch on this one
+        ends._memory = (res["evidence"], res["h_max"], event)
+    made["memory_buffers"] = res
+    return FusedGrid(*(res[n] if n in o["want"] else None for n in hip_ops.GROUND_FUSE_WANT), x0=x0, y0=y0, cell=cell)
+
+
 def _run_obstacles(ends, step, made) -> Obstacles:
     """The obstacle list of a step's grid (Statement O, objcavit_amd/obstacles.py): one call (at most seven launches) for the batch, on
-    the grid's own buffers behind its launches on the same stream -- the grid's cells are per image whatever the frames' sizes."""
+    the grid's own buffers behind its launches on the same stream -- the grid's cells are per image whatever the frames' sizes.  With
+    ``ground_memory=dict(obstacles=True)`` it reads the FUSED ``state`` and ``h_max`` of the step instead (``count`` / ``obstacle`` null:
+    the rows' point counts are 0)."""
     o, g = ends.obstacles, made["ground_buffers"]
+    if ends.memory is not None and ends.memory["obstacles"]:
+        f = made["memory_buffers"]
+        g = {"state": f["state"], "count": None, "obstacle": None, "h_max": f["h_max"]}
     x0, y0, cell, GX, GY = ends.ground["grid"]
     want = tuple(n for n in hip_ops.OBSTACLES_WANT if n != "labels" or o["labels"])
     res = hip_ops.obstacles(g["state"], (x0, y0, cell, GX, GY), count=g["count"], obstacle=g["obstacle"], h_max=g["h_max"], link=o["link"],
@@ -463,37 +535,47 @@ DERIVED_READOUTS = (
              lambda o: (), ("K",), _run_obstacles, slice(5)),
 )
 ALL_READOUTS = READOUTS + DERIVED_READOUTS
-for _r in ALL_READOUTS:
+# The readouts that carry state from one step to the next.  They run behind READOUTS and IN FRONT OF DERIVED_READOUTS (the obstacle list
+# may read the fused map), so they have a table of their own: ``ALL_READOUTS`` ends with the grid and its list, as it did.
+# ``ground_memory`` reads the grid's buffers of the same step and the memory of the previous one (``_Ends._memory``).
+TEMPORAL_READOUTS = (
+    _Readout("ground_memory", "ground_memory", "memory", lambda kw, lo, hi: _memory_options(kw["ground_memory"], kw["ground_grid"] is not None),
+             lambda o: (), ("K",), _run_memory, slice(4)),
+)
+RUN_ORDER = READOUTS + TEMPORAL_READOUTS + DERIVED_READOUTS          # every readout, in the order of their launches
+for _r in RUN_ORDER:
     setattr(PredictResult, _r.attr, None)          # an ATTRIBUTE, not a field: ``PredictResult``'s fields are what they were
 
 
 class _ObjectsResult(PredictResult):
     """A ``PredictResult`` -- same fields, same tuple -- whose attributes named in ``READOUTS`` (``objects`` / ``points`` /
     ``object_metrics`` / ``normals`` / ``plane`` / ``ground``) or in ``DERIVED_READOUTS`` (``obstacles``) hold the step's ``ObjectDepths`` /
-    ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals`` / ``GroundPlane`` / ``GroundGrid`` / ``Obstacles``; each is a keyword of its own
-    and survives ``_replace``."""
+    ``PointCloud`` / ``ObjectMetrics`` / ``SurfaceNormals`` / ``GroundPlane`` / ``GroundGrid`` / ``Obstacles``, and ``ground_memory``
+    (``TEMPORAL_READOUTS``) the step's ``FusedGrid``; each is a keyword of its own and survives ``_replace``."""
 
     def __new__(cls, *fields, **kw):
-        made = {r.attr: kw.pop(r.attr, None) for r in ALL_READOUTS}
+        made = {r.attr: kw.pop(r.attr, None) for r in RUN_ORDER}
         self = super().__new__(cls, *fields, **kw)
         self.__dict__.update(made)
         return self
 
     def _replace(self, **kw):
-        return _ObjectsResult(*PredictResult(*self)._replace(**kw), **{r.attr: getattr(self, r.attr) for r in ALL_READOUTS})
+        return _ObjectsResult(*PredictResult(*self)._replace(**kw), **{r.attr: getattr(self, r.attr) for r in RUN_ORDER})
 
 
-class _Step(namedtuple("_Step", ["depth_gt", "boxes", "K", "frames", "pose", "size"])):
+class _Step(namedtuple("_Step", ["depth_gt", "boxes", "K", "frames", "pose", "size", "memory"], defaults=(None,))):
     """The inputs of one step beside the forward's (``_Ends.step``): the ground truth as the caller gave it, the boxes as (xywh, counts),
     the intrinsics of the source frames [B, 4] and the camera poses [B, 12] on the device (each None when absent or when no keyword
-    reads it), the frame batches and the step's final size.  ``PipelinedPredictor`` hands it through its slot pipeline in the place
-    of the ground truth."""
+    reads it), the frame batches and the step's final size; ``memory``: None without the ``ground_memory`` keyword, else the step's
+    part of it -- {"motion": fp32 [B, 4] on the device or None (the identity), "reset": bool} and, once the step has run, "prev": what
+    it read of the previous step (``_run_memory``), so that a re-run reads the same.  ``PipelinedPredictor`` hands it through its slot
+    pipeline in the place of the ground truth."""
     __slots__ = ()
 
     def held(self) -> List[torch.Tensor]:
         """The tensors among them that a pipeline slot's launches read (the frames' own are held with the ingest's)."""
         gt = [self.depth_gt] if isinstance(self.depth_gt, torch.Tensor) else list(self.depth_gt or [])
-        return gt + list(self.boxes or ()) + [t for t in (self.K, self.pose) if t is not None]
+        return gt + list(self.boxes or ()) + [t for t in (self.K, self.pose, (self.memory or {}).get("motion")) if t is not None]
 
 
 def _window(args, Hs: int, Ws: int, crop) -> Tuple[int, int, int, int]:
@@ -611,13 +693,14 @@ class _Ends:
         self.lens = lens
         self._rect = (None, None)                    # (the frame list last ingested through the lens with ``resize``, its RGB24 copies)
         self.min_depth, self.max_depth = _depth_range(args)
-        given = {r.keyword: readouts.pop(r.keyword, None) for r in ALL_READOUTS}
+        given = {r.keyword: readouts.pop(r.keyword, None) for r in RUN_ORDER}
         if readouts:
             raise TypeError(f"_Ends: unknown keyword(s) {sorted(readouts)}")
-        for r in ALL_READOUTS:                       # .errors, .readout, .cloud, .normals, .plane, .ground, .obstacles: the parsed keyword or None
+        for r in RUN_ORDER:                          # .errors, .readout, .cloud, .normals, .plane, .ground, .memory, .obstacles: the parsed keyword or None
             setattr(self, r.options, r.parse(given, self.min_depth, self.max_depth))
         self.cloud_normals = _cloud_normals(given["point_cloud"])          # a normal per point of the cloud
-        self.readouts = tuple((r, r.maps(getattr(self, r.options))) for r in ALL_READOUTS if getattr(self, r.options) is not None)
+        self.readouts = tuple((r, r.maps(getattr(self, r.options))) for r in RUN_ORDER if getattr(self, r.options) is not None)
+        self._memory = None                          # ``ground_memory``: (evidence, h_max, event) of the newest step, None before the first
         self.vmin = self.min_depth if vmin is None else float(vmin)
         self.vmax = self.max_depth if vmax is None else float(vmax)
         self.u16_scale = depth_factor(args) if u16_scale is None else float(u16_scale)
@@ -807,6 +890,23 @@ class _Ends:
             raise ValueError(f"camera_pose: one row-major 3 x 4 [R | t] per frame ([{B}, 12]), got {tuple(camera_pose.shape)}")
         return camera_pose.to(device=device, dtype=torch.float32).contiguous()
 
+    def motion_on(self, ego_motion, reset: bool, device, B: int) -> Optional[dict]:
+        """The ``memory`` entry of a step record: None without the ``ground_memory`` keyword, else {"motion", "reset"} with the step's
+        ``ego_motion`` -- [B, 3] = (dx, dy, dyaw) per frame (``ground_memory.ego_motion`` makes (cos, sin, dx, dy) of it) or [B, 4]
+        as that function returns it, a tensor or a list -- as fp32 [B, 4] on the device; None stays None: the identity, a standing
+        camera."""
+        if self.memory is None:
+            return None
+        if ego_motion is None:
+            return {"motion": None, "reset": bool(reset)}
+        m = ego_motion if isinstance(ego_motion, torch.Tensor) else torch.as_tensor(ego_motion, dtype=torch.float64)
+        if m.dim() != 2 or int(m.shape[0]) != B or int(m.shape[1]) not in (3, 4):
+            raise ValueError(f"ego_motion: one (dx, dy, dyaw) or (cos, sin, dx, dy) per frame ([{B}, 3] or [{B}, 4]), got {tuple(m.shape)}")
+        if int(m.shape[1]) == 3:
+            m = m.detach().to("cpu", torch.float64)
+            m = _ego_motion(m[:, 0], m[:, 1], m[:, 2])
+        return {"motion": m.to(device=device, dtype=torch.float32).contiguous(), "reset": bool(reset)}
+
     def _shift(self, device, top: int, left: int) -> torch.Tensor:
         ent = self._on(device, False)
         key = ("shift", top, left)
@@ -814,18 +914,19 @@ class _Ends:
             ent[key] = torch.tensor([0.0, 0.0, float(left), float(top)], dtype=torch.float32, device=device)
         return ent[key]
 
-    def step(self, frames: list, size: Optional[Tuple[int, int]] = None, depth_gt=None, boxes=None, intrinsics=None, camera_pose=None) -> _Step:
-        """The step record of a call's keywords: boxes padded, intrinsics and poses uploaded, on the current stream.  ``size``: the
-        frames' window size where the caller has it already."""
+    def step(self, frames: list, size: Optional[Tuple[int, int]] = None, depth_gt=None, boxes=None, intrinsics=None, camera_pose=None,
+             ego_motion=None, reset: bool = False) -> _Step:
+        """The step record of a call's keywords: boxes padded, intrinsics, poses and motions uploaded, on the current stream.  ``size``:
+        the frames' window size where the caller has it already."""
         B, dev = sum(int(f.shape[0]) for f in frames), frames[0].device
         return _Step(depth_gt, self.boxes_on(boxes, dev, B), self.intrinsics_on(intrinsics, dev, B), frames,
-                     self.pose_on(camera_pose, dev, B), size or self.window_of(frames))
+                     self.pose_on(camera_pose, dev, B), size or self.window_of(frames), self.motion_on(ego_motion, reset, dev, B))
 
     def finish(self, out, mirror, step: _Step, first_image_id: int, want: Tuple[str, ...]) -> PredictResult:
         """Final map + (with ground truth) the metric launch, on the current stream, from the outputs of the un-mirrored and (or None)
         the mirrored forward; their ``depth_var`` / ``confidence`` are read when ``want`` names "depth_std" / "confidence".  Behind them
         every readout of ``READOUTS`` whose keyword is set and whose ``needs`` the step has, in that order: the per-object error right
-        behind the metric launch, the object readout, the point cloud, the normals, the ground plane, the occupancy grid, then ``DERIVED_READOUTS``: the obstacle list of that grid.  The maps they
+        behind the metric launch, the object readout, the point cloud, the normals, the ground plane, the occupancy grid, then ``TEMPORAL_READOUTS``: the ground memory, then ``DERIVED_READOUTS``: the obstacle list of that grid (or of the fused map).  The maps they
         read are made even when ``want`` leaves them out (and are then not handed out)."""
         asked = want
         live = [r for r, _ in self.readouts if None not in [getattr(step, n) for n in r.needs]]
@@ -968,6 +1069,17 @@ class Predictor:
     ``obstacles`` ATTRIBUTE holds the ``Obstacles`` (cells, metres [B, capacity, 8], counts, total [B], labels or None; None otherwise).
     The grid's ``state``, ``count``, ``obstacle`` and ``h_max`` are made for it even when the grid's ``want`` leaves them out;
     ``result.ground`` still hands out only what was asked for.  Pass it by keyword.
+    ``ground_memory``: None, or a dict with some of ``free`` (2), ``occupied`` (4), ``decay`` (1), ``limit`` (32), ``free_at`` (4),
+    ``occupied_at`` (6), ``want`` (a subset of "evidence", "state", "h_max", "first_occupied"), ``obstacles`` (False) -- the grid fused
+    over the calls of THIS predictor, every image of the batch a camera stream of its own (objcavit_amd/ground_memory.py, Statement F).
+    Refused at construction without ``ground_grid=``.  With it, one more launch behind the grid's (and in front of the obstacle list's)
+    carries the previous call's evidence through ``ego_motion=`` of the call -- [B, 3] = (dx, dy, dyaw) since the previous call, or
+    [B, 4] as ``ground_memory.ego_motion`` returns it, a tensor or a list, uploaded like ``camera_pose``; None: the camera stood --,
+    adds this call's grid, and the result's ``ground_memory`` ATTRIBUTE holds the ``FusedGrid`` (None otherwise).  ``reset=True`` on a
+    call forgets before that call.  The grid's ``state`` and ``h_max`` are made for it even when the grid's ``want`` leaves them out.
+    ``obstacles=True`` makes the ``obstacles=`` keyword's list from the FUSED ``state`` and ``h_max`` (``points`` / ``obstacle_points`` of
+    a row are then 0); otherwise the list reads the frame's grid as without the memory.  Every result's tensors are fresh: the memory
+    keeps the newest by reference and overwrites nothing.  Pass them by keyword.
     ``object_metrics``: None, or a dict with some of ``shrink`` / ``regions`` -- the depth error per box and over objects against
     background (objcavit_amd/object_metrics.py).  With it, a call that has both ``depth_gt`` and ``boxes=`` (in pixels of the ground
     truth's grid) issues one more call right behind the metric launch, on the tensors that launch reads, and the result's
@@ -977,14 +1089,14 @@ class Predictor:
     def __init__(self, model, args, flip_tta: bool = True, loss: bool = False, colormap=None, vmin: Optional[float] = None,
                  vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
                  ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None,
-                 obstacles: Optional[dict] = None, pixel_format=None,
+                 obstacles: Optional[dict] = None, ground_memory: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         self.model = model
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
                           resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
                           object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid,
-                          ground_plane=ground_plane, obstacles=obstacles)
+                          ground_plane=ground_plane, obstacles=obstacles, ground_memory=ground_memory)
         self.flip_tta = flip_tta
 
     def _forward(self, frames: List[torch.Tensor], B: int):
@@ -998,13 +1110,14 @@ class Predictor:
 
     @torch.no_grad()
     def __call__(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, want: Sequence[str] = ("depth",),
-                 camera_pose=None, intrinsics=None, boxes=None) -> PredictResult:
+                 ego_motion=None, reset: bool = False, camera_pose=None, intrinsics=None, boxes=None) -> PredictResult:
         want = _check_want(want)
         if _need_stats(want) or ((intrinsics is not None or self.ends.has_default_K) and (_cloud_want(self.ends.cloud) or _cloud_want(self.ends.plane) or _cloud_want(self.ends.ground))):
             _turn_stats_on(self.model)
         frames = self.ends.frames_of(frames_u8, "frames_u8")
         out, mirror = self._forward(frames, sum(int(f.shape[0]) for f in frames))
-        step = self.ends.step(frames, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose)
+        step = self.ends.step(frames, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose,
+                              ego_motion=ego_motion, reset=reset)
         return self.ends.finish(out, mirror, step, first_image_id, want)
 
 
@@ -1023,6 +1136,11 @@ class PipelinedPredictor(_SlotPipeline):
     the normals; the pose is uploaded in ``submit`` and held like the frames.  ``ground_plane``: as ``Predictor``'s, on the slot's stream
     between the normals and the grid, no host read; with ``ground_grid=dict(pose="plane")`` the grid reads the step's own estimate.
     ``obstacles``: as ``Predictor``'s, on the slot's stream behind the grid, no host read; its tensors are recorded like the grid's.
+    ``ground_memory`` / ``submit(..., ego_motion=, reset=)``: as ``Predictor``'s, fused in SUBMISSION order: the first state that crosses
+    steps.  The slots run on streams of their own, so a step's fuse launch waits (on the device) for the event the previous step's
+    recorded; only that launch is ordered, the forwards overlap as before.  A step that ``collect`` re-runs (fp16 range guard) is fused
+    again from the previous evidence and the motion it had read, and the memory is not advanced a second time: the steps behind it have
+    fused its FIRST map (``_run_memory``).
     ``object_metrics``: as ``Predictor``'s, on the slot's stream behind the step's metric launch; a re-run step gets its table from the re-run's forward.  ``resize``: as ``Predictor``'s; the
     graphs are captured for (H, W), a step's window may have another size than the example's (one size within a step) and its outputs
     have that size; a size's tap tables are uploaded when it is first submitted; a re-run step is resized again from its kept frames.
@@ -1043,7 +1161,7 @@ class PipelinedPredictor(_SlotPipeline):
                  flip_tta: bool = True, loss: bool = False, want: Sequence[str] = ("depth",), colormap=None,
                  vmin: Optional[float] = None, vmax: Optional[float] = None, u16_scale: Optional[float] = None, surface_normals: Optional[dict] = None,
                  ground_grid: Optional[dict] = None, lens: Optional[LensMap] = None, ground_plane: Optional[dict] = None,
-                 obstacles: Optional[dict] = None, pixel_format=None,
+                 obstacles: Optional[dict] = None, ground_memory: Optional[dict] = None, pixel_format=None,
                  crop: Optional[Tuple[int, int, int, int]] = None, resize: Optional[Tuple[int, int]] = None,
                  object_metrics: Optional[dict] = None, point_cloud: Optional[dict] = None, object_depth: Optional[dict] = None):
         super().__init__(slots)
@@ -1052,7 +1170,7 @@ class PipelinedPredictor(_SlotPipeline):
         self.ends = _Ends(args, flip_tta=flip_tta, loss=loss, colormap=colormap, vmin=vmin, vmax=vmax, u16_scale=u16_scale, crop=crop,
                           resize=resize, pixel_format=pixel_format, lens=lens, object_depth=object_depth, point_cloud=point_cloud,
                           object_metrics=object_metrics, surface_normals=surface_normals, ground_grid=ground_grid,
-                          ground_plane=ground_plane, obstacles=obstacles)
+                          ground_plane=ground_plane, obstacles=obstacles, ground_memory=ground_memory)
         if _need_stats(self.want) or _cloud_want(self.ends.cloud) or _cloud_want(self.ends.plane) or _cloud_want(self.ends.ground):
             _turn_stats_on(model)                            # before the captures below: a graph reads the flag when it is captured
         self.flip_tta = flip_tta
@@ -1080,7 +1198,7 @@ class PipelinedPredictor(_SlotPipeline):
         return self._collect()
 
     def submit(self, frames_u8: Frames, depth_gt=None, first_image_id: int = 0, object_features=None, object_xywh_list=None,
-               camera_pose=None, intrinsics=None, boxes=None) -> None:
+               ego_motion=None, reset: bool = False, camera_pose=None, intrinsics=None, boxes=None) -> None:
         """Enqueue one predict step on the next slot's stream; returns at once.  ``boxes``: the boxes of the step's frames
         (``object_depth`` / ``object_metrics`` keywords); lists are padded here, on the caller's stream, and the tensors are held like the frames.
         ``intrinsics``: the frames' (fx, fy, cx, cy) for the point cloud (``point_cloud`` keyword), uploaded here and held likewise;
@@ -1097,7 +1215,8 @@ class PipelinedPredictor(_SlotPipeline):
         taps = self.ends.taps_of(frames)
         yuv = self.ends.yuv_of(frames)
         self.ends.lens_of(frames)                    # ``lens``: the map's device copy is made HERE when the device is new; it is kept for good
-        step = self.ends.step(frames, size, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose)
+        step = self.ends.step(frames, size, depth_gt=depth_gt, boxes=boxes, intrinsics=intrinsics, camera_pose=camera_pose,
+                              ego_motion=ego_motion, reset=reset)
         held = list(taps or ()) + ([] if yuv is None else [yuv]) + _tensors_of(frames) + step.held()
         self._submit(frames, held, step, first_image_id, (object_features, object_xywh_list))
         made = self._pending[-1].result
